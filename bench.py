@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native MITgcm hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one FORWARD_STEP of the device-resident hot path (DYNAMICS ->
 SOLVE_FOR_PRESSURE/CG2D -> MOMENTUM_CORRECTION_STEP -> INTEGR_CONTINUITY ->
@@ -10,7 +10,14 @@ line.  `value` is BASELINE config 2 (90x40x15, one tile): at N>1 (one process pe
 GPU, torch.distributed.run) every rank runs an independent replica ("replicas
 only") and value = the sum over ranks.
 
-Fields of the JSON line beyond the driver contract:
+A plain run sets the model up, warms up, times the K steps and prints the line (metric,
+value, unit, ms_per_step, ...).  --dump-outputs DIR writes the state the K-th timed step
+left (dump_outputs) as DIR/<name>.npy.  Everything below takes runs of its own and is
+measured with --full only.
+
+Fields of the JSON line with --full:
+  kernel_ms_mean, kernel_ms_layout
+               the same K steps again, eagerly, with HIP events around every launch
   roofline     dominant kernel (the whole-solve CG2D): bound "latency" -- the f64
                VALU issue of the CU(s) it runs on plus per-iteration barriers;
                us_per_iteration, the VALU floor and, for completeness, its
@@ -45,6 +52,7 @@ CG2D_F64_OPS_PER_POINT_ITER = 9 + 9 + 2 + 2 + 2 + 6
 CU_F64_LANE_OPS_PER_CLK = 64
 CLOCK_GHZ = 2.4                # MI355X peak engine clock (s_memtime/s_memrealtime: 2.40 GHz measured)
 MOM_BYTES_PER_POINT = {15: 116.8, 50: 107.8}   # fused momentum, algorithmic
+MAX_BATCH = 4096               # steps one mgcm_forward_step call takes (its solve records: model.hip maxRec)
 PMC_TAG = {"global_ocean.90x40x15": "ocean90", "global_ocean.cs32x15": "cs32x15", "llc90_synthetic": "llc90"}
 
 
@@ -58,6 +66,12 @@ def parse():
     ap.add_argument("--config", default="global_ocean.90x40x15",
                     choices=["global_ocean.90x40x15", "global_ocean.cs32x15", "llc90_synthetic", "global_oce_latlon_90x40x15", "tutorial_global_oce_latlon", "baroclinic_gyre_dst3",
                              "tutorial_baroclinic_gyre", "tutorial_barotropic_gyre"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the per-kernel event "
+                         "pass and the rooflines, the STREAM triad, the cs32x15 sub-record (N = 1), the CPU "
+                         "baselines, the sharded records (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the model state the last timed step left as DIR/<name>.npy (float64; rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--shard", action="store_true",
                     help="N>1: shard the workload's tiles over the N processes (RCCL, strong scaling, "
@@ -415,6 +429,26 @@ def check_iters(iters, what):
                                                                                          iters))
 
 
+DUMP_FIELDS = ("uVel", "vVel", "wVel", "theta", "salt", "etaN")   # what FORWARD_STEP hands its caller
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(m, path):
+    """The prognostic state as the timed steps left it, one float64 <name>.npy per field of
+    DUMP_FIELDS (every tile with its halo, as Model.get returns it).  Past DUMP_MAX_BYTES in
+    all (the LLC-90 synthetic) each field is cut to the same number of points, drawn once
+    from numpy default_rng(0) and sorted, so two builds dump the same points."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {n: m.get(n) for n in DUMP_FIELDS}
+    per_field = DUMP_MAX_BYTES // (8 * len(arrs))
+    for n, a in arrs.items():
+        if a.size > per_field and sum(x.nbytes for x in arrs.values()) > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per_field, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def resident_ms(config, steps, warmup, device):
     """ms/step of the resident (1-GPU, graph-replayed) path of a workload, and its model;
     the caller closes the model."""
@@ -439,7 +473,7 @@ def cs32x15_record(a, device):
     graph-replayed step, `steps` timed after `warmup`, with its own attribution pass and
     rooflines.  Reported beside `value` (config 2), not instead of it."""
     cfg = "global_ocean.cs32x15"
-    steps, warmup = max(2, a.steps), a.warmup
+    steps, warmup = min(max(2, a.steps), MAX_BATCH), min(a.warmup, MAX_BATCH)
     m, ms, iters, el = resident_ms(cfg, steps, warmup, device)
     dt_clock = m.params["deltaTClock"]
     iters_t, kern, layout, roof, roof_hbm = attribution(m, m, steps, cfg, default_pmc_summary(cfg), m.sync)
@@ -593,7 +627,7 @@ def main():
     # MGCM_SHARD_BACKEND=gloo: host-staged transport, lets several ranks share one GPU
     # (rehearsal on a 1-GPU box; RCCL refuses two ranks per device)
     shard_backend = os.environ.get("MGCM_SHARD_BACKEND", "nccl")
-    sharded_rec = world > 1 and not shard and not a.no_sharded
+    sharded_rec = a.full and world > 1 and not shard and not a.no_sharded
     if world > 1 or shard:
         import torch
         import torch.distributed as dist
@@ -666,8 +700,11 @@ def main():
     if graph_shard:
         stepper.capture_step()            # one eager step, then the capture
         stepper.replay(max(1, a.warmup // 2))
-    elif a.warmup > 0:
+    elif shard and a.warmup > 0:
         stepper.forward_step(a.warmup)
+    else:
+        for w in range(0, a.warmup, MAX_BATCH):
+            m.forward_step(min(MAX_BATCH, a.warmup - w))
     sync()
 
     def barrier():
@@ -677,13 +714,23 @@ def main():
     if not shard:
         m.prepare()
     # timed region: K steps replayed from hipGraphs (kernel timing off)
+    iters_early = []
     barrier()
     sync()
     t0 = time.perf_counter()
     if graph_shard:
         stepper.replay(a.steps // 2)
-    else:
+    elif shard:
         stepper.forward_step(a.steps)
+    else:
+        # the library keeps the solve records of one call, MAX_BATCH steps at the most: a longer
+        # run is timed as back-to-back calls, each but the last checked before the next starts
+        left = a.steps
+        while left > MAX_BATCH:
+            m.forward_step(MAX_BATCH)
+            iters_early += [int(v) for v in m.solve_history(MAX_BATCH)[0]]
+            left -= MAX_BATCH
+        m.forward_step(left)
     sync()
     t1 = time.perf_counter()
     barrier()
@@ -693,15 +740,20 @@ def main():
                          device="cuda" if shard and dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    iters = [int(v) for v in m.solve_history(a.steps)[0]]
-    if a.pmc_summary is None:
-        a.pmc_summary = default_pmc_summary(a.config)
-    iters_t, kern, layout, roofline, roofline_hbm = attribution(m, stepper, a.steps, a.config, a.pmc_summary, sync)
+    iters = iters_early + [int(v) for v in m.solve_history(a.steps - len(iters_early))[0]]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(m, a.dump_outputs)
+    iters_t = []
+    if a.full:
+        if a.pmc_summary is None:
+            a.pmc_summary = default_pmc_summary(a.config)
+        iters_t, kern, layout, roofline, roofline_hbm = attribution(m, stepper, min(a.steps, MAX_BATCH), a.config,
+                                                                    a.pmc_summary, sync)
     # sanity: the solution is finite and the solver converged every step
     stats = m.solve_stats()
     eta = m.get("etaN")
     assert np.isfinite(eta).all() and stats["cg2d_last_res"] < 1e-6, stats
-    # every solve of both batches converged without a hand-off timeout
+    # every solve of the timed batch (and of --full's eager pass) converged without a hand-off timeout
     check_iters(iters + iters_t, a.config)
     model_days = a.steps * dt_clock / 86400.0
     copies = 1 if shard else world   # independent model integrations in the job
@@ -742,27 +794,32 @@ def main():
         # graphs over the first 20 graph-replayed steps (results identical either way)
         "thermo_overlap": _overlap_info(m),
         "cg2d_mean_iters_per_solve": iters_total / max(1, len(iters)),
-        "kernel_ms_mean": {k: v[0] for k, v in kern.items()},
-        # those times: an eager pass of the same steps with events around every launch, in the
-        # launch layout the timed graph replays (one stream: a second-stream THERMODYNAMICS,
-        # C5's, is serialised there); with the fused grids "mom_step" is k_dt_l1+l2+l3
-        "kernel_ms_layout": {"eager_pass_of_the_graph_layout": True, **layout},
-        "roofline": roofline,
-        "roofline_hbm": roofline_hbm,
+        "full": a.full,
     })
+    if a.full:
+        out.update({
+            "kernel_ms_mean": {k: v[0] for k, v in kern.items()},
+            # those times: an eager pass of the same steps with events around every launch, in the
+            # launch layout the timed graph replays (one stream: a second-stream THERMODYNAMICS,
+            # C5's, is serialised there); with the fused grids "mom_step" is k_dt_l1+l2+l3
+            "kernel_ms_layout": {"eager_pass_of_the_graph_layout": True, **layout},
+            "roofline": roofline,
+            "roofline_hbm": roofline_hbm,
+        })
     m.close()
-    # the measured STREAM triad of this box beside the 8 TB/s spec
-    try:
-        triad = stream_triad_gbs(local)
-        out["roofline_hbm"]["stream_triad_gbs"] = triad
-        out["roofline_hbm"]["frac_of_triad"] = out["roofline_hbm"]["achieved"] / triad
-    except Exception as e:   # a reference number only: its absence does not fail the bench
-        out["roofline_hbm"]["stream_triad_gbs"] = None
-        print("bench: stream triad not measured: %s" % e, file=sys.stderr)
-    if rank == 0 and world == 1 and not shard and a.config != "global_ocean.cs32x15" and not a.no_cs32:
+    if a.full:
+        # the device's measured STREAM triad beside the 8 TB/s spec
+        try:
+            triad = stream_triad_gbs(local)
+            out["roofline_hbm"]["stream_triad_gbs"] = triad
+            out["roofline_hbm"]["frac_of_triad"] = out["roofline_hbm"]["achieved"] / triad
+        except Exception as e:   # a reference number only: its absence does not fail the bench
+            out["roofline_hbm"]["stream_triad_gbs"] = None
+            print("bench: stream triad not measured: %s" % e, file=sys.stderr)
+    if a.full and rank == 0 and world == 1 and not shard and a.config != "global_ocean.cs32x15" and not a.no_cs32:
         # the other half of BASELINE.json's metric, timed in the same run
         out["cs32x15"] = cs32x15_record(a, local)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:   # the CPU baseline is an N=1 line
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:   # the CPU baseline is an N=1 line
         out["cpu_baseline"] = cpu_baseline(a.config, a.cpu_seconds)
     if sharded_rec:
         import threading

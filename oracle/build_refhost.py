@@ -1,5 +1,6 @@
-"""Build the reference-host harness mitgcm_amd/fortran/refhost/refhost_<layout> (needs the
-reference headers: the build container only; the binaries travel to the GPU box).
+"""Build the reference-host harness oracle/_ref/refhost_<layout> from the sources of
+mitgcm_amd/fortran/refhost (needs the reference headers: where they are absent, the binaries
+built beforehand under oracle/_ref/ are used as they are; oracle/_ref/ is never committed).
 
 The MODS drop-ins (mitgcm_amd/fortran/mods/*.F), the harness main program
 (refhost/refhost.F) and REFHOST_PARAM / REFHOST_FIELD -- generated here from the
@@ -33,11 +34,14 @@ import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+ROOT = os.path.dirname(HERE)
 REF = "/root/reference"
 FC = "/opt/rocm/bin/amdflang"
-MODS = os.path.join(HERE, "mods")
-RH = os.path.join(HERE, "refhost")
+FDIR = os.path.join(ROOT, "mitgcm_amd", "fortran")
+MODS = os.path.join(FDIR, "mods")
+RH = os.path.join(FDIR, "refhost")
+# the binaries carry code compiled from the reference's headers: they go where git never looks
+OUT = os.path.join(HERE, "_ref")
 # the package switches genmake2 derives from the experiment's packages.conf (the packages
 # whose headers the drop-ins and the harness include)
 OCEAN90 = ("global_ocean.90x40x15", "#define ALLOW_GMREDI\n#define ALLOW_CD_CODE\n")
@@ -106,7 +110,7 @@ def generate_fill(path):
     incl = [ln for ln in body.splitlines() if ln.startswith("#") and "include" in ln or ln.startswith("# include")
             or ln.startswith("#ifdef") or ln.startswith("#endif")]
     calls = _calls(mirror)
-    head = ['C refhost_fill.F -- GENERATED by mitgcm_amd/fortran/build_refhost.py from the calls of',
+    head = ['C refhost_fill.F -- GENERATED by oracle/build_refhost.py from the calls of',
             'C MGCM_AMD_MIRROR (mods/mgcm_amd_mirror.F); do not edit.',
             '#include "PACKAGES_CONFIG.h"', '#include "CPP_OPTIONS.h"', '#ifdef ALLOW_GMREDI',
             '# include "GMREDI_OPTIONS.h"', '#endif', '']
@@ -221,9 +225,10 @@ def build(layouts=("ref", "1t", "cs32", "cs32_6t", "llc30"), verbose=False):
                     print(" ".join(cmd))
                 subprocess.run(cmd, check=True, cwd=tmp)
                 objs.append(o)
-            exe = os.path.join(RH, "refhost_" + lay)
+            os.makedirs(OUT, exist_ok=True)
+            exe = os.path.join(OUT, "refhost_" + lay)
             cmd = [FC, "-o", exe + ".tmp"] + objs + ["-L" + os.path.dirname(lib), "-lmitgcm_amd",
-                                                      "-Wl,-rpath,$ORIGIN/../.."]
+                                                      "-Wl,-rpath,$ORIGIN/../../mitgcm_amd"]
             subprocess.run(cmd, check=True, cwd=tmp)
             os.replace(exe + ".tmp", exe)
             out.append(exe)

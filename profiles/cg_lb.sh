@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=gpurun_out/$1
 mkdir -p $O
 for lb in 0 1 2 3 0; do
-  MGCM_CG2D_LB=$lb timeout -k 10 200 python bench.py --steps 300 --warmup 30 --no-cs32 --no-cpu-baseline \
+  MGCM_CG2D_LB=$lb timeout -k 10 200 python bench.py --full --steps 300 --warmup 30 --no-cs32 --no-cpu-baseline \
     > $O/bench_lb$lb.json 2> $O/bench_lb$lb.err || { tail -20 $O/bench_lb$lb.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/bench_lb$lb.json').read().strip().splitlines()[-1])

@@ -13,6 +13,6 @@ for c in global_ocean.90x40x15 global_ocean.cs32x15 llc90_synthetic baroclinic_g
   [ "$c" = global_ocean.90x40x15 ] && args="--steps 400 --warmup 20"
   [ "$c" = global_ocean.cs32x15 ] && args="--steps 200 --warmup 10"
   [ "$c" = baroclinic_gyre_dst3 ] && args="--steps 400 --warmup 20"
-  timeout -k 10 600 python bench.py --config $c $args --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed"; tail -20 $O/bench_$c.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $c $args --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed"; tail -20 $O/bench_$c.err; exit 1; }
   python -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', 'ms/step %.4f' % d['ms_per_step'], d['thermo_overlap'])"
 done

@@ -8,7 +8,7 @@ timeout -k 10 1000 python -u -m pytest -x -v --timeout 300 --timeout-method thre
 tail -3 $O/pytest.log
 run() {  # name config steps env...
   local name=$1 c=$2 n=$3; shift 3
-  env "$@" timeout -k 10 300 python bench.py --config $c --steps $n --warmup 20 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --config $c --steps $n --warmup 20 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
   python -c "import json; d=json.load(open('$O/$name.json')); k=d['kernel_ms_mean']; print('%-16s step %.4f' % ('$name', d['ms_per_step']), {a: round(b*1e3,1) for a,b in k.items()})"
 }
 run c2_fused global_ocean.90x40x15 400

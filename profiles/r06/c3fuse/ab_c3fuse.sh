@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_cs32x15.py tests/test_gpu_a
 tail -1 $OUT/pytest_ab.log
 for rep in 1 2 3; do
   for mask in 3469 15757; do
-    MGCM_STEP_FUSE=$mask timeout -k 10 200 python3 bench.py --config global_ocean.cs32x15 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c3_m${mask}_$rep.json 2> $OUT/c3_m${mask}_$rep.err || { echo bench failed; tail -5 $OUT/c3_m${mask}_$rep.err; exit 1; }
+    MGCM_STEP_FUSE=$mask timeout -k 10 200 python3 bench.py --full --config global_ocean.cs32x15 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c3_m${mask}_$rep.json 2> $OUT/c3_m${mask}_$rep.err || { echo bench failed; tail -5 $OUT/c3_m${mask}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c3_m${mask}_$rep.json')); print('C3 mask=$mask', round(d['ms_per_step'],4), round(d['cg2d_mean_iters_per_solve'],1))"
   done
 done

@@ -11,7 +11,7 @@ timeout -k 10 200 python3 tools/refhost_case.py ref 4 $OUT/case > $OUT/case.log 
 run() {
   local tag=$1; shift
   env "$@" MGCM_AMD_MODELS=4 MGCM_AMD_EAGER=0 MGCM_CG2D_MWG=0 MGCM_AMD_CAPTURE=multi,debug \
-    timeout -k 10 120 mitgcm_amd/fortran/refhost/refhost_ref $OUT/case tests/golden/global_ocean.90x40x15/input > $OUT/$tag.log 2>&1
+    timeout -k 10 120 oracle/_ref/refhost_ref $OUT/case tests/golden/global_ocean.90x40x15/input > $OUT/$tag.log 2>&1
   local rc=$?
   echo "$tag rc=$rc: $(grep -c 'capture\[' $OUT/$tag.log) stage lines; last: $(grep 'capture\[' $OUT/$tag.log | tail -1)"
   return 0

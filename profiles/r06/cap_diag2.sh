@@ -13,7 +13,7 @@ timeout -k 10 200 python3 tools/refhost_case.py ref 4 $CASE > $OUT/case.log 2>&1
 for cfg in "4 1" "3 1" "4 0"; do
   set -- $cfg
   MGCM_OVERLAP=$2 MGCM_AMD_MODELS=$1 MGCM_AMD_EAGER=0 MGCM_CG2D_MWG=0 MGCM_AMD_CAPTURE=multi,debug \
-    timeout -k 10 120 mitgcm_amd/fortran/refhost/refhost_ref $CASE tests/golden/global_ocean.90x40x15/input > $OUT/m$1_ovl$2.log 2>&1
+    timeout -k 10 120 oracle/_ref/refhost_ref $CASE tests/golden/global_ocean.90x40x15/input > $OUT/m$1_ovl$2.log 2>&1
   echo "models=$1 overlap=$2 rc=$?: $(grep -c 'MGCM_AMD ' $OUT/m$1_ovl$2.log) lines"
   grep "MGCM_AMD capture\|MGCM_AMD   op" $OUT/m$1_ovl$2.log | tail -4
 done

@@ -11,7 +11,7 @@ MGCM_DT_ORDER=1 timeout -k 10 300 python -u -m pytest tests/test_gpu_ocean90.py 
 tail -1 $OUT/pytest.log
 for rep in 1 2 3; do
   for o in 0 1; do
-    MGCM_DT_ORDER=$o timeout -k 10 200 python3 bench.py --config global_ocean.90x40x15 --steps 200 --warmup 20 --no-cpu-baseline --no-cs32 > $OUT/c2_o${o}_$rep.json 2> $OUT/c2_o${o}_$rep.err || { echo bench failed; tail -5 $OUT/c2_o${o}_$rep.err; exit 1; }
+    MGCM_DT_ORDER=$o timeout -k 10 200 python3 bench.py --full --config global_ocean.90x40x15 --steps 200 --warmup 20 --no-cpu-baseline --no-cs32 > $OUT/c2_o${o}_$rep.json 2> $OUT/c2_o${o}_$rep.err || { echo bench failed; tail -5 $OUT/c2_o${o}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c2_o${o}_$rep.json')); k=d['kernel_ms_mean']; print('C2 order=$o', round(d['ms_per_step'],4), {a: round(b*1e3,1) for a, b in k.items() if b > 0.005})"
   done
 done

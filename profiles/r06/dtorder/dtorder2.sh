@@ -12,13 +12,13 @@ MGCM_DT_LF=2 timeout -k 10 300 python -u -m pytest tests/test_gpu_ocean90.py -m 
 tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for m in 0 7 2; do
-    MGCM_DT_LF=$m timeout -k 10 200 python3 bench.py --config global_ocean.90x40x15 --steps 200 --warmup 20 --no-cpu-baseline --no-cs32 > $OUT/c2_m${m}_$rep.json 2> $OUT/c2_m${m}_$rep.err || { echo bench failed; tail -5 $OUT/c2_m${m}_$rep.err; exit 1; }
+    MGCM_DT_LF=$m timeout -k 10 200 python3 bench.py --full --config global_ocean.90x40x15 --steps 200 --warmup 20 --no-cpu-baseline --no-cs32 > $OUT/c2_m${m}_$rep.json 2> $OUT/c2_m${m}_$rep.err || { echo bench failed; tail -5 $OUT/c2_m${m}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c2_m${m}_$rep.json')); print('C2 mask=$m', round(d['ms_per_step'],4), round(d['kernel_ms_mean']['mom_step']*1e3,1))"
   done
 done
 for m in 0 7 2; do
   export MGCM_DT_LF=$m
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m$m -o run --output-format csv -- python3 bench.py --config global_ocean.90x40x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_m$m.log 2>&1 || { echo prof failed; tail -5 $OUT/prof_m$m.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m$m -o run --output-format csv -- python3 bench.py --full --config global_ocean.90x40x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_m$m.log 2>&1 || { echo prof failed; tail -5 $OUT/prof_m$m.log; exit 1; }
   python3 - $OUT/prof_m$m $m <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_stats.csv", recursive=True)[0]

@@ -10,7 +10,7 @@ mkdir -p $OUT
 for rep in 1 2; do
 for m in 0 7 2; do
   export MGCM_DT_LF=$m
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m${m}_$rep -o run --output-format csv -- python3 bench.py --config global_ocean.90x40x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_m${m}_$rep.json 2> $OUT/prof_m${m}_$rep.err || { echo prof failed; tail -5 $OUT/prof_m${m}_$rep.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_m${m}_$rep -o run --output-format csv -- python3 bench.py --full --config global_ocean.90x40x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_m${m}_$rep.json 2> $OUT/prof_m${m}_$rep.err || { echo prof failed; tail -5 $OUT/prof_m${m}_$rep.err; exit 1; }
   python3 - $OUT/prof_m${m}_$rep $m <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_stats.csv", recursive=True)[0]

@@ -10,13 +10,13 @@ mkdir -p $OUT
 for rep in 1 2 3; do
   for o in 0 4; do
     if [ $o = 0 ]; then unset MGCM_DT_LAYOUT; else export MGCM_DT_LAYOUT=$o; fi
-    timeout -k 10 200 python3 bench.py --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/c3_l${o}_$rep.json 2> $OUT/c3_l${o}_$rep.err || { echo bench failed; tail -5 $OUT/c3_l${o}_$rep.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/c3_l${o}_$rep.json 2> $OUT/c3_l${o}_$rep.err || { echo bench failed; tail -5 $OUT/c3_l${o}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c3_l${o}_$rep.json')); print('C3 layout=$o', round(d['ms_per_step'],4))"
   done
 done
 for o in 0 4; do
   if [ $o = 0 ]; then unset MGCM_DT_LAYOUT; else export MGCM_DT_LAYOUT=$o; fi
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_l$o -o run --output-format csv -- python3 bench.py --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_l$o.json 2> $OUT/prof_l$o.err || { echo prof failed; tail -5 $OUT/prof_l$o.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_l$o -o run --output-format csv -- python3 bench.py --full --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/prof_l$o.json 2> $OUT/prof_l$o.err || { echo prof failed; tail -5 $OUT/prof_l$o.err; exit 1; }
   python3 - $OUT/prof_l$o $o <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_stats.csv", recursive=True)[0]

@@ -11,7 +11,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for tm in 0 2 3; do
     if [ $tm = 0 ]; then unset MGCM_TRACER_MARCH; else export MGCM_TRACER_MARCH=$tm; fi
-    timeout -k 10 200 python3 bench.py --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_tm${tm}_$rep.json 2> $OUT/llc_tm${tm}_$rep.err || { echo bench failed; tail -5 $OUT/llc_tm${tm}_$rep.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_tm${tm}_$rep.json 2> $OUT/llc_tm${tm}_$rep.err || { echo bench failed; tail -5 $OUT/llc_tm${tm}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/llc_tm${tm}_$rep.json')); k=d['kernel_ms_mean']; print('LLC tm=$tm', round(d['ms_per_step'],4), {a: round(b,4) for a, b in k.items() if 'tr' in a or 'thermo' in a})"
   done
 done

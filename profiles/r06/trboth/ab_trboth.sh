@@ -15,12 +15,12 @@ MGCM_TR_BOTH=0 timeout -k 10 300 python -u -m pytest tests/test_gpu_cs32x15.py -
 tail -1 $OUT/pytest_pair.log
 for rep in 1 2 3; do
   for b in 0 1; do
-    MGCM_TR_BOTH=$b timeout -k 10 200 python3 bench.py --config global_ocean.cs32x15 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c3_b${b}_$rep.json 2> $OUT/c3_b${b}_$rep.err || { echo bench failed; tail -5 $OUT/c3_b${b}_$rep.err; exit 1; }
+    MGCM_TR_BOTH=$b timeout -k 10 200 python3 bench.py --full --config global_ocean.cs32x15 --steps 200 --warmup 20 --no-cpu-baseline > $OUT/c3_b${b}_$rep.json 2> $OUT/c3_b${b}_$rep.err || { echo bench failed; tail -5 $OUT/c3_b${b}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c3_b${b}_$rep.json')); print('C3 both=$b', round(d['ms_per_step'],4))"
   done
 done
 for b in 0 1; do
-  MGCM_TR_BOTH=$b timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof$b -o run --output-format csv -- python3 bench.py --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof$b.json 2> $OUT/prof$b.err || { echo rocprof failed; tail -5 $OUT/prof$b.err; exit 1; }
+  MGCM_TR_BOTH=$b timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof$b -o run --output-format csv -- python3 bench.py --full --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof$b.json 2> $OUT/prof$b.err || { echo rocprof failed; tail -5 $OUT/prof$b.err; exit 1; }
   f=$(find $OUT/prof$b -name "*kernel_stats.csv" | head -1)
   python3 -c "
 import csv

@@ -12,7 +12,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for m2 in 1 2; do
     export MGCM_TRACER_MARCH2=$m2
-    timeout -k 10 200 python3 bench.py --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_m2${m2}_$rep.json 2> $OUT/llc_m2${m2}_$rep.err || { echo bench failed; tail -5 $OUT/llc_m2${m2}_$rep.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_m2${m2}_$rep.json 2> $OUT/llc_m2${m2}_$rep.err || { echo bench failed; tail -5 $OUT/llc_m2${m2}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/llc_m2${m2}_$rep.json')); print('LLC m2=$m2', round(d['ms_per_step'],4))"
   done
 done

@@ -13,7 +13,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2 3; do
   for v in base trw3; do
     if [ $v = base ]; then unset MGCM_LIB; else export MGCM_LIB=$V; fi
-    timeout -k 10 200 python3 bench.py --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/c3_${v}_$rep.json 2> $OUT/c3_${v}_$rep.err || { echo bench failed; tail -5 $OUT/c3_${v}_$rep.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --config global_ocean.cs32x15 --steps 100 --warmup 10 --no-cpu-baseline --no-cs32 > $OUT/c3_${v}_$rep.json 2> $OUT/c3_${v}_$rep.err || { echo bench failed; tail -5 $OUT/c3_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/c3_${v}_$rep.json')); print('C3 $v', round(d['ms_per_step'],4), 'temp_step', round(d['kernel_ms_mean'].get('temp_step',0)*1e3,1))"
   done
 done

@@ -14,13 +14,13 @@ tail -1 $OUT/pytest3.log
 for rep in 1 2; do
   for v in orig b2 b3; do
     case $v in orig) E="MGCM_LIB=$PWD/mitgcm_amd/_build/diag/lib_vi_orig.so" ;; b2) E="MGCM_VI_LBW=2" ;; b3) E="MGCM_VI_LBW=3" ;; esac
-    env $E timeout -k 10 200 python3 bench.py --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_${v}_$rep.json 2> $OUT/llc_${v}_$rep.err || { echo bench failed; tail -5 $OUT/llc_${v}_$rep.err; exit 1; }
+    env $E timeout -k 10 200 python3 bench.py --full --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_${v}_$rep.json 2> $OUT/llc_${v}_$rep.err || { echo bench failed; tail -5 $OUT/llc_${v}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/llc_${v}_$rep.json')); k=d['kernel_ms_mean']; print('LLC $v', round(d['ms_per_step'],4), 'mom_step ms', round(k['mom_step'],4))"
   done
 done
 for v in orig b2 b3; do
   case $v in orig) E="MGCM_LIB=$PWD/mitgcm_amd/_build/diag/lib_vi_orig.so" ;; b2) E="MGCM_VI_LBW=2" ;; b3) E="MGCM_VI_LBW=3" ;; esac
-  env $E timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$v -o run --output-format csv -- python3 bench.py --config llc90_synthetic --steps 30 --warmup 4 --no-cpu-baseline --no-cs32 > $OUT/prof_$v.json 2> $OUT/prof_$v.err || { echo rocprof failed; tail -5 $OUT/prof_$v.err; exit 1; }
+  env $E timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$v -o run --output-format csv -- python3 bench.py --full --config llc90_synthetic --steps 30 --warmup 4 --no-cpu-baseline --no-cs32 > $OUT/prof_$v.json 2> $OUT/prof_$v.err || { echo rocprof failed; tail -5 $OUT/prof_$v.err; exit 1; }
   f=$(find $OUT/prof_$v -name "*kernel_stats.csv" | head -1)
   python3 -c "
 import csv

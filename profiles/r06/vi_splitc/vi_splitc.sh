@@ -12,12 +12,12 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_llc.py -m gpu -x -v -s --ti
 tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for sc in 0 1; do
-    MGCM_VI_SPLITC=$sc timeout -k 10 200 python3 bench.py --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_sc${sc}_$rep.json 2> $OUT/llc_sc${sc}_$rep.err || { echo bench failed; tail -5 $OUT/llc_sc${sc}_$rep.err; exit 1; }
+    MGCM_VI_SPLITC=$sc timeout -k 10 200 python3 bench.py --full --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_sc${sc}_$rep.json 2> $OUT/llc_sc${sc}_$rep.err || { echo bench failed; tail -5 $OUT/llc_sc${sc}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/llc_sc${sc}_$rep.json')); k=d['kernel_ms_mean']; print('LLC sc=$sc', round(d['ms_per_step'],4), 'mom_step ms', round(k['mom_step'],4))"
   done
 done
 for sc in 0 1; do
-  MGCM_VI_SPLITC=$sc timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof$sc -o run --output-format csv -- python3 bench.py --config llc90_synthetic --steps 30 --warmup 4 --no-cpu-baseline --no-cs32 > $OUT/prof$sc.json 2> $OUT/prof$sc.err || { echo rocprof failed; tail -5 $OUT/prof$sc.err; exit 1; }
+  MGCM_VI_SPLITC=$sc timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof$sc -o run --output-format csv -- python3 bench.py --full --config llc90_synthetic --steps 30 --warmup 4 --no-cpu-baseline --no-cs32 > $OUT/prof$sc.json 2> $OUT/prof$sc.err || { echo rocprof failed; tail -5 $OUT/prof$sc.err; exit 1; }
   f=$(find $OUT/prof$sc -name "*kernel_stats.csv" | head -1)
   python3 -c "
 import csv

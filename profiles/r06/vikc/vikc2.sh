@@ -11,7 +11,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2 3; do
   for kc in 0 25; do
     if [ $kc = 0 ]; then unset MGCM_VI_KC; else export MGCM_VI_KC=$kc; fi
-    timeout -k 10 200 python3 bench.py --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_kc${kc}_$rep.json 2> $OUT/llc_kc${kc}_$rep.err || { echo bench failed; tail -5 $OUT/llc_kc${kc}_$rep.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --config llc90_synthetic --steps 40 --warmup 6 --no-cpu-baseline --no-cs32 > $OUT/llc_kc${kc}_$rep.json 2> $OUT/llc_kc${kc}_$rep.err || { echo bench failed; tail -5 $OUT/llc_kc${kc}_$rep.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/llc_kc${kc}_$rep.json')); print('LLC kc=$kc', round(d['ms_per_step'],4), 'mom', round(d['kernel_ms_mean']['mom_step']*1e3,1))"
   done
 done

@@ -17,9 +17,9 @@ if [ "$MODE" = tests ]; then
   tail -5 $O/pytest.log
   exit $rc
 fi
-timeout -k 10 300 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -20 $O/bench_n1.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -20 $O/bench_n1.err; exit 1; }
 MGCM_SHARD_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 \
   > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err || { tail -20 $O/bench_n2_gloo.err; exit 1; }
 python -c "
 import json,sys

@@ -21,13 +21,13 @@ if [ "$MODE" = tests ] || [ "$MODE" = all ]; then
   cat $O/smoke.log
 fi
 if [ "$MODE" = bench ] || [ "$MODE" = all ] || [ "$MODE" = prof ]; then
-  timeout -k 10 600 python bench.py --config $CONFIG $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $CONFIG $BENCH_ARGS > $O/bench.json 2> $O/bench.err || { echo bench failed; tail -30 $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 if [ "$MODE" = prof ] || [ "$MODE" = all ]; then
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --config $CONFIG $BENCH_ARGS --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err || { echo rocprof failed; tail -30 $O/prof.err; exit 1; }
-  timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run --output-format csv -- python3 bench.py --config $CONFIG --steps 20 --warmup 2 --no-cpu-baseline $PMC_ARGS > $O/pmc_fetch.json 2> $O/pmc_fetch.err || { echo pmc fetch failed; tail -30 $O/pmc_fetch.err; exit 1; }
-  timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o run --output-format csv -- python3 bench.py --config $CONFIG --steps 20 --warmup 2 --no-cpu-baseline $PMC_ARGS > $O/pmc_write.json 2> $O/pmc_write.err || { echo pmc write failed; tail -30 $O/pmc_write.err; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --config $CONFIG $BENCH_ARGS --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.err || { echo rocprof failed; tail -30 $O/prof.err; exit 1; }
+  timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o run --output-format csv -- python3 bench.py --full --config $CONFIG --steps 20 --warmup 2 --no-cpu-baseline $PMC_ARGS > $O/pmc_fetch.json 2> $O/pmc_fetch.err || { echo pmc fetch failed; tail -30 $O/pmc_fetch.err; exit 1; }
+  timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write -o run --output-format csv -- python3 bench.py --full --config $CONFIG --steps 20 --warmup 2 --no-cpu-baseline $PMC_ARGS > $O/pmc_write.json 2> $O/pmc_write.err || { echo pmc write failed; tail -30 $O/pmc_write.err; exit 1; }
   if [ -x tools/pmc_calib ]; then
     timeout -s KILL 60 rocprofv3 --pmc FETCH_SIZE -d $O/calib_fetch -o run --output-format csv -- tools/pmc_calib > $O/calib.log 2>&1 || { echo calib fetch failed; tail $O/calib.log; exit 1; }
     timeout -s KILL 60 rocprofv3 --pmc WRITE_SIZE -d $O/calib_write -o run --output-format csv -- tools/pmc_calib >> $O/calib.log 2>&1 || { echo calib write failed; tail $O/calib.log; exit 1; }

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 tail -2 $O/pytest.log
 run() {  # name env...
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --config llc90_synthetic --steps 20 --warmup 4 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --config llc90_synthetic --steps 20 --warmup 4 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
   python -c "import json; d=json.load(open('$O/$name.json')); k=d['kernel_ms_mean']; print('%-14s step %.4f' % ('$name', d['ms_per_step']), {a: round(b*1e3,1) for a,b in k.items() if b}, d['thermo_overlap'])"
 }
 run at1s MGCM_THERMO_AT=1 MGCM_TRACER_PAIR=0 MGCM_TR_KC=5 MGCM_VI_KC=10 MGCM_MWG_EXCL=0

@@ -12,7 +12,7 @@ MGCM_VI_GL=1 timeout -k 10 400 python -u -m pytest -x -q --timeout 300 --timeout
   -k "vi or None" > $O/llc_parity.log 2>&1; r=$?; tail -2 $O/llc_parity.log
 [ $r -eq 0 ] || exit $r
 for v in 0 1 0 1 0 1; do
-  MGCM_VI_GL=$v timeout -k 10 200 python bench.py --config llc90_synthetic --steps 40 --warmup 4 --no-cs32 \
+  MGCM_VI_GL=$v timeout -k 10 200 python bench.py --full --config llc90_synthetic --steps 40 --warmup 4 --no-cs32 \
     --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err || { tail -20 $O/bench_$v.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/bench_$v.json').read().strip().splitlines()[-1])

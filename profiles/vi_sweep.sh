@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 O=gpurun_out/vi_sweep; mkdir -p $O
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --config llc90_synthetic --steps 10 --warmup 2 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
+  env "$@" timeout -k 10 200 python bench.py --full --config llc90_synthetic --steps 10 --warmup 2 --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "$name failed"; tail -5 $O/$name.err; return 1; }
   python -c "import json; d=json.load(open('$O/$name.json')); k=d['kernel_ms_mean']; print('%-22s step %.4f  mom %.1f us  temp %.1f  cg2d %.1f' % ('$name', d['ms_per_step'], 1e3*k['mom_step'], 1e3*k['temp_step'], 1e3*k['cg2d']))"
 }
 run base

@@ -11,7 +11,7 @@ O=gpurun_out/$1
 mkdir -p $O
 for v in new 3469 3533 new 3469 3533 new 3469 3533; do
   if [ $v = new ]; then unset MGCM_STEP_FUSE; else export MGCM_STEP_FUSE=$v; fi
-  timeout -k 10 200 python bench.py --config llc90_synthetic --steps 40 --warmup 4 --no-cs32 \
+  timeout -k 10 200 python bench.py --full --config llc90_synthetic --steps 40 --warmup 4 --no-cs32 \
     --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err || { tail -20 $O/bench_$v.err; exit 1; }
   python -c "
 import json; d=json.loads(open('$O/bench_$v.json').read().strip().splitlines()[-1])

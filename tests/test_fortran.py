@@ -98,7 +98,7 @@ def test_refhost_builds_against_reference_headers():
     generated COMMON-block fill routines compile against the reference's headers (its own
     SIZE.h and the one-tile layout) and link the library."""
     import sys
-    sys.path.insert(0, os.path.join(ROOT, "mitgcm_amd", "fortran"))
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import build_refhost
     params, fields = build_refhost.mirror_calls()
     assert ("R", "monitorFreq") in params and ("I", "nEndIter") in params

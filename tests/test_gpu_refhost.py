@@ -1,5 +1,5 @@
 """The drop-in boundary run the way a reference build runs it: mitgcm_amd/fortran/refhost
-(mitgcm_amd/fortran/build_refhost.py) is compiled against the reference's own headers, so
+(oracle/build_refhost.py) is compiled against the reference's own headers, so
 the model state lives in the reference's COMMON blocks (DYNVARS.h, GRID.h, SURFACE.h,
 FFIELDS.h, CG2D.h, GMREDI.h, ...), and steps FORWARD_STEP's routine sequence by calling
 the MODS shims under their reference names -- DO_OCEANIC_PHYS(myTime, myIter, myThid),
@@ -42,13 +42,14 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RH = os.path.join(ROOT, "mitgcm_amd", "fortran", "refhost")
+REFBIN = os.path.join(ROOT, "oracle", "_ref")   # the harness binaries (oracle/build_refhost.py)
 CHECK = ("uVel", "vVel", "wVel", "theta", "salt", "etaN", "etaH", "gU", "gV", "guNm1", "gvNm1", "gtNm1", "gsNm1",
          "rhoInSitu", "totPhiHyd", "hFacC", "hFacW", "rStarFacC", "aW2d", "pC", "uVelD", "etaNm1", "Kwx", "dEtaHdt")
 NSTEPS = 6
 
 
 def _mirror_calls(undef=()):
-    sys.path.insert(0, os.path.join(ROOT, "mitgcm_amd", "fortran"))
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import build_refhost
     return build_refhost.mirror_calls(undef)
 
@@ -141,8 +142,8 @@ def _read_out(path, state_names, nsteps):
     ("ref", 0, 1, 1, 0, 0), ("ref", 0, 3, 1, 0, 0), ("1t", 0, 1, 0, 0, 1)])
 def test_refhost_mods_dropins_bitexact(layout, refOrder, models, mwg, eager, packages, tmp_path):
     from mitgcm_amd import configs
-    exe = os.path.join(RH, "refhost_" + layout)
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_" + layout)
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     tiles = {"ref": (9, 4), "1t": (1, 1)}[layout]
 
     def cfg():
@@ -218,8 +219,8 @@ def test_refhost_mods_dropins_bitexact(layout, refOrder, models, mwg, eager, pac
 def test_refhost_dropin_throughput(io, register, models, cap, tmp_path):
     from mitgcm_amd import configs
     nsteps = 60
-    exe = os.path.join(RH, "refhost_ref")
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_ref")
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     m = configs.make_model(lambda: configs.global_ocean_90x40x15(nSx=9, nSy=4))
     extra = [("dumpFreq", 0.0)] if io == "off" else []
     state = _write_blob(tmp_path / "refhost_in.bin", m, nsteps, monitor_days=10 * nsteps, extra=extra)
@@ -292,8 +293,8 @@ def _cs32_namelists(dst):
     ("cs32", 3, 1, 0), ("cs32_6t", 1, 0, 0), ("cs32_6t", 2, 0, 0), ("cs32_6t", 3, 0, 0), ("cs32_6t", 6, 0, 0)])
 def test_refhost_cs32_exch2_bitexact(layout, models, mwg, eager, tmp_path):
     from mitgcm_amd import configs
-    exe = os.path.join(RH, "refhost_" + layout)
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_" + layout)
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     nsteps = 4
     sNy = 16 if layout == "cs32" else 32
 
@@ -400,8 +401,8 @@ def _llc_namelists(dst, params, tRef, sRef, delR, g):
 @pytest.mark.parametrize("models,eager", [(1, 0), (1, 1), (3, 0), (4, 0), (13, 0)])
 def test_refhost_llc30_exch2_bitexact(models, eager, tmp_path):
     from mitgcm_amd import configs
-    exe = os.path.join(RH, "refhost_llc30")
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_llc30")
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     nsteps = 4
     out3 = configs.llc_synthetic(n=30)
     g0, params, st0 = out3
@@ -460,8 +461,8 @@ def test_refhost_llc30_exch2_bitexact(models, eager, tmp_path):
 @pytest.mark.parametrize("layout,models", [("ref", 2), ("ref", 3), ("ref", 4), ("cs32_6t", 3), ("cs32_6t", 6)])
 def test_refhost_multistream_capture(layout, models, tmp_path):
     from mitgcm_amd import configs
-    exe = os.path.join(RH, "refhost_" + layout)
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_" + layout)
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     nsteps = 4
     if layout == "ref":
         m = configs.make_model(lambda: configs.global_ocean_90x40x15(nSx=9, nSy=4))
@@ -501,8 +502,8 @@ def test_refhost_multistream_capture(layout, models, tmp_path):
 @pytest.mark.parametrize("layout,models,mwg", [("ref", 2, 0), ("ref", 4, 0), ("ref", 2, 1), ("cs32_6t", 2, 0)])
 def test_refhost_virtual_gpus(layout, models, mwg, tmp_path):
     from mitgcm_amd import configs
-    exe = os.path.join(RH, "refhost_" + layout)
-    assert os.path.exists(exe), "refhost not built (mitgcm_amd/fortran/build_refhost.py, __graft_entry__.build())"
+    exe = os.path.join(REFBIN, "refhost_" + layout)
+    assert os.path.exists(exe), "refhost not built (oracle/build_refhost.py, __graft_entry__.build())"
     nsteps = 4
 
     def cfg():

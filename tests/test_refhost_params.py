@@ -22,9 +22,9 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "mitgcm_amd", "fortran", "refhost", "refhost_ref")
+REFBIN = os.path.join(ROOT, "oracle", "_ref")   # the harness binaries (oracle/build_refhost.py)
 PARAM_DIR = os.path.join(ROOT, "tests", "golden", "global_ocean.90x40x15", "input")
-sys.path.insert(0, os.path.join(ROOT, "mitgcm_amd", "fortran"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 # device name -> the COMMON variable the mirror passes under it, where they differ:
 # uniform vertical profiles by their first level (the mirror refuses non-uniform ones), the
@@ -73,7 +73,7 @@ EXPERIMENTS = {"global_ocean.90x40x15": ("ref", {"selectVortScheme", "temp_EvPrR
 @pytest.mark.parametrize("exp", sorted(EXPERIMENTS))
 def test_refhost_resolves_the_namelist_as_the_reference(exp, tmp_path):
     layout, unset_ok, cfg_skip = EXPERIMENTS[exp]
-    exe = os.path.join(ROOT, "mitgcm_amd", "fortran", "refhost", "refhost_" + layout)
+    exe = os.path.join(REFBIN, "refhost_" + layout)
     if not os.path.exists(exe):
         pytest.skip("refhost not built (needs the reference headers)")
     out = tmp_path / "params.txt"
@@ -121,7 +121,7 @@ def test_refhost_resolves_the_llc_namelist_as_configured(tmp_path):
     namelist from configs.llc_synthetic's parameters; refhost (layout "llc30") must resolve it
     back to the same values (the GPU test then pins every mirror parameter against the device
     model's own)."""
-    exe = os.path.join(ROOT, "mitgcm_amd", "fortran", "refhost", "refhost_llc30")
+    exe = os.path.join(REFBIN, "refhost_llc30")
     if not os.path.exists(exe):
         pytest.skip("refhost not built (needs the reference headers)")
     from mitgcm_amd import configs

@@ -10,7 +10,7 @@ mkdir -p $OUT
 for r in 1 2; do
   for a in ${ARMS:-base:}; do
     n=${a%%:*}; e=${a#*:}
-    env ${e//,/ } timeout -k 10 200 python bench.py --config $CONFIG --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_${n}_$r.json 2> $OUT/e_${n}_$r.err || { echo "bench $n failed"; tail -5 $OUT/e_${n}_$r.err; exit 1; }
+    env ${e//,/ } timeout -k 10 200 python bench.py --full --config $CONFIG --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_${n}_$r.json 2> $OUT/e_${n}_$r.err || { echo "bench $n failed"; tail -5 $OUT/e_${n}_$r.err; exit 1; }
     python3 -c "import json; d=json.load(open('$OUT/b_${n}_$r.json')); print('$CONFIG', '$n', $r, round(d['ms_per_step'],4))"
   done
 done

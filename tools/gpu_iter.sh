@@ -13,10 +13,10 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 for c in ${CONFIGS:-global_ocean.90x40x15 llc90_synthetic}; do
   case $c in llc90_synthetic) A="--steps 48 --warmup 4";; global_ocean.cs32x15) A="--steps 100 --warmup 10";; *) A="--steps 200 --warmup 20";; esac
-  timeout -k 10 300 python bench.py --config $c $A --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "bench $c failed"; tail -30 $OUT/bench_$c.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c $A --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { echo "bench $c failed"; tail -30 $OUT/bench_$c.err; exit 1; }
   python -c "import json,sys; d=json.load(open('$OUT/bench_$c.json')); print('$c', round(d['ms_per_step'],4), 'ms/step', round(d['value'],2), d['unit'], {k: round(v*1e3,1) for k,v in d['kernel_ms_mean'].items()})"
   if [ "${PROF:-1}" = 1 ]; then
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$c -o run --output-format csv -- python3 bench.py --config $c $A --no-cpu-baseline > /dev/null 2> $OUT/prof_$c.err || { echo "rocprof $c failed"; tail -20 $OUT/prof_$c.err; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$c -o run --output-format csv -- python3 bench.py --full --config $c $A --no-cpu-baseline > /dev/null 2> $OUT/prof_$c.err || { echo "rocprof $c failed"; tail -20 $OUT/prof_$c.err; exit 1; }
     python - <<PY
 import csv, glob
 f = glob.glob("$OUT/prof_$c/**/*kernel_stats.csv", recursive=True)[0]

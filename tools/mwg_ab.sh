@@ -11,7 +11,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for c in llc90_synthetic global_ocean.cs32x15; do
     st=24; [ $c = global_ocean.cs32x15 ] && st=200
-    timeout -k 10 200 python bench.py --config $c --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_$c.json 2> $OUT/e_$c.err || { echo "bench $c failed"; tail -20 $OUT/e_$c.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --config $c --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_$c.json 2> $OUT/e_$c.err || { echo "bench $c failed"; tail -20 $OUT/e_$c.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/b_$c.json')); print('$c', 'ms/step %.4f' % d['ms_per_step'], 'cg2d us/it %.3f' % d['roofline']['us_per_iteration'])"
   done
 done

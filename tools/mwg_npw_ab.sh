@@ -12,7 +12,7 @@ for v in ${VARS:-def 1 2 4}; do
   lib=mitgcm_amd/libmitgcm_amd.so; [ $v != def ] && lib=mitgcm_amd/libmitgcm_amd_npw$v.so
   for c in llc90_synthetic global_ocean.cs32x15; do
     st=24; [ $c = global_ocean.cs32x15 ] && st=200
-    MGCM_LIB=$lib timeout -k 10 200 python bench.py --config $c --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$c.json 2> $OUT/e_${v}_$c.err || { echo "bench $v $c failed"; tail -20 $OUT/e_${v}_$c.err; exit 1; }
+    MGCM_LIB=$lib timeout -k 10 200 python bench.py --full --config $c --steps $st --warmup 10 --no-cpu-baseline > $OUT/b_${v}_$c.json 2> $OUT/e_${v}_$c.err || { echo "bench $v $c failed"; tail -20 $OUT/e_${v}_$c.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/b_${v}_$c.json')); print('npw $v $c', 'ms/step %.4f' % d['ms_per_step'], 'cg2d us/it %.3f' % d['roofline']['us_per_iteration'])"
   done
 done

@@ -15,6 +15,6 @@ for c in ${CONFIGS:-global_ocean.90x40x15}; do
   args="--steps 30 --warmup 4"
   [ "$c" = global_ocean.90x40x15 ] && args="--steps 200 --warmup 20"
   [ "$c" = global_ocean.cs32x15 ] && args="--steps 100 --warmup 10"
-  timeout -k 10 600 python bench.py --config $c $args --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed"; tail -20 $O/bench_$c.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --config $c $args --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed"; tail -20 $O/bench_$c.err; exit 1; }
   python -c "import json; d=json.load(open('$O/bench_$c.json')); print('$c', 'ms/step %.4f' % d['ms_per_step'], 'value %.1f' % d['value'], {k: round(v*1e3,1) for k,v in d['kernel_ms_mean'].items()})"
 done

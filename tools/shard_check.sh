@@ -20,7 +20,7 @@ for c in ${CONFIGS:-llc90_synthetic global_ocean.cs32x15}; do
   for mode in resident shard; do
     extra=""
     [ $mode = shard ] && extra="--shard"
-    timeout -k 10 400 python bench.py --config $c $args --no-cpu-baseline $extra > $O/bench_${c}_$mode.json 2> $O/bench_${c}_$mode.err || { echo "bench $c $mode failed"; tail -20 $O/bench_${c}_$mode.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --config $c $args --no-cpu-baseline $extra > $O/bench_${c}_$mode.json 2> $O/bench_${c}_$mode.err || { echo "bench $c $mode failed"; tail -20 $O/bench_${c}_$mode.err; exit 1; }
     python -c "import json; d=json.load(open('$O/bench_${c}_$mode.json')); print('$c $mode', d['config'].get('cg2d'), 'ms/step %.4f' % d['ms_per_step'], {k: round(v*1e3,1) for k,v in d['kernel_ms_mean'].items()})"
   done
 done
