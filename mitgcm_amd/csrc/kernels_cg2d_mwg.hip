@@ -386,7 +386,8 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
   // from cg2d_x, written before this launch, and scaled with the owner's arithmetic)
 #pragma unroll
   for (int m = 0; m < MW_OPT; m++) s_l[m * MW_NT + tid] = x[m];
-  for (int qq = tid; qq < nImp; qq += MW_NT) {
+  // (every ring-1 slot, also the unused ones past nImp: the ring's r below reads them)
+  for (int qq = tid; qq < (nImp > NR ? nImp : NR); qq += MW_NT) {
     const double xv = f.cg2d_x[T.impG[gi + qq]];
     s_l[NO + qq] = p.cg2dNormaliseRHS ? xv * rhsNorm : xv;
   }

@@ -735,7 +735,15 @@ static int build_mwg(mgcm_model *m) {
       impC[(size_t)g * IMAX + NR + n] = expSlot[ring2[g][n]];
       impG[(size_t)g * IMAX + NR + n] = g2of(ring2[g][n]);
     }
-    nImp[g] = NR + (int)ring2[g].size();
+    // the import slots run to the end of ring 2, or of ring 1 where there is no ring 2: the
+    // unused ring-1 slots in front of a ring 2 poll export granule 0, which a part whose
+    // stencils stay inside it (one part, periodic onto itself: no point exported) never gets.
+    // This shortens the import sweep of every part without a ring 2 (e.g. the one-row parts
+    // of a 126 x 3 box), not only of the lone part.  Their ring-1 slots past nImp keep the
+    // value k_cg2d_mwg's prologue reads at impG's padding, cg2d_x(1,1,t0): it only ever meets
+    // the zero coefficients of an inactive ring slot, and were it NaN or Inf the 0*NaN would
+    // stay in r_l / s_l slots that no stencil of an active point names.
+    nImp[g] = ring2[g].empty() ? (int)ring1[g].size() : NR + (int)ring2[g].size();
   }
   MwgTables &T = m->mwg;
   T = MwgTables{};
