@@ -236,11 +236,15 @@ int mgcm_field_pack(mgcm_model *m, const char *name, const long *idx, long n, do
  * the model's halo map; the cross-process sources must have been delivered first). */
 int mgcm_exchange_field(mgcm_model *m, const char *name);
 
-/* Wait for all queued device work. */
+/* Wait for all queued device work.  Fails when a step's CG2D solve found a non-zero
+ * right-hand side or first guess on a land point of a block its tables leave out (the
+ * solve is recorded with numIters = -1; mgcm_forward_step then fails too). */
 int mgcm_sync(mgcm_model *m);
 
 /* Device CG2D on fields of this model (cg2d.F:13 semantics; b is normalised in
- * place).  b and x are host arrays of nTiles*(sNx+2OLx)*(sNy+2OLy) doubles. */
+ * place).  b and x are host arrays of nTiles*(sNx+2OLx)*(sNy+2OLy) doubles.  Where b or
+ * x is non-zero on a land point of a block the solver's tables leave out, the model goes
+ * over to the tables of the whole grid and solves with those. */
 int mgcm_cg2d(mgcm_model *m, double *cg2d_b, double *cg2d_x, double *firstResidual,
               double *minResidualSq, double *lastResidual, int *numIters, int *nIterMin);
 

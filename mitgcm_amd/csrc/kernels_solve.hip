@@ -846,13 +846,15 @@ template <int BX, int BY, int NT, bool MINRES, bool FMA, bool SR = false>
 __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, const unsigned *__restrict__ nbx,
                                                  const int *__restrict__ blkx, int nBlk, int maxIters, int nIterMinIn,
                                                  SolveRecord *rec, int *stepCounter, const int *__restrict__ slot2,
-                                                 const long *__restrict__ srcOf) {
+                                                 const long *__restrict__ srcOf, const int *__restrict__ dropG,
+                                                 int nDrop, int *guardHit) {
   constexpr int NPT = BX * BY, NP = NPT * NT, NB = 2 * (BX + BY), NW = NT / 64;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double *r_l = lds;               // NP + 1 (last = ZERO slot)
   double *s_l = lds + (NP + 1);
-  double *red = lds + 2 * (NP + 1);  // 4 x 16 partial slots
+  double *red = lds + 2 * (NP + 1);  // 4 x 16 partial slots, then the guard word red[64]
   const int tid = threadIdx.x;
+  if (tid == 0) red[64] = 0.0;
   const bool act = tid < nBlk;
   const int bt = act ? tid : 0;
   const double az = act ? 1.0 : 0.0;
@@ -898,6 +900,14 @@ __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, con
       aC[b][a] = az * f.aC2d[G[b][a]];
       pC[b][a] = az * f.pC[G[b][a]];
     }
+  // The points of the all-land blocks left out of the tables (model.hip build_nbr, dropG): the
+  // solve is exact only while b and the first guess are 0.0 on them, so they are scanned here,
+  // beside the coefficient loads; a non-zero (or NaN) marks the solve as failed (numIters = -1)
+  bool dropBad = false;
+  for (int q = tid; q < nDrop; q += NT) {
+    const long g = dropG[q];
+    dropBad |= !(f.cg2d_b[g] == 0.0) | !(f.cg2d_x[g] == 0.0);
+  }
   double x[BY][BX], r[BY][BX], sv[BY][BX], bb[BY][BX];
 #pragma unroll
   for (int b = 0; b < BY; b++)
@@ -959,6 +969,7 @@ __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, con
 #pragma unroll
     for (int a = 0; a < BX; a++) s_l[cs[b][a]] = x[b][a];
   if (tid == 0) { s_l[NP] = 0.0; r_l[NP] = 0.0; }
+  if (dropBad) red[64] = 1.0;   // after block_max_nw's barrier, which orders it behind the clearing store
   __syncthreads();
   double err = 0.0, sumB = 0.0;
   {
@@ -1250,8 +1261,10 @@ __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, con
     R.minResidualSq = minResidualSq;
     R.rhsMax = rhsMax;
     R.sumRHS = sumRHS;
-    R.numIters = actualIts;
+    const bool failed = red[64] != 0.0;   // the guard above: a dropped land point held a non-zero
+    R.numIters = failed ? -1 : actualIts;
     R.nIterMin = nIterMin;
+    if (failed && guardHit) *guardHit = 1;
   }
 }
 
@@ -1709,9 +1722,17 @@ hipError_t launch_cg2d_block(const Dims &d, const Params &p, const Fields &f, co
 // BX x BY blocks, at most NT of them).  Fewer, fatter threads trade serial work per thread
 // for cheaper reductions and barriers (fewer waves).
 struct CgxGeom { int bx, by, nt; };
-// measured on global_ocean.90x40x15 (profiles/r02/ocean90/cg2d_geometry.txt): fatter threads
-// (3x4, 5x4, 3x8, 5x8) spill the per-point registers and run 1.5-8x slower per iteration
-static const CgxGeom CGX[] = {{2, 4, 512}, {2, 2, 1024}};
+// measured on global_ocean.90x40x15: with 320-384 threads (a 256-VGPR budget) the fatter
+// blocks 3x4, 5x4, 3x8, 5x8 spill and run 1.5-8x slower per iteration
+// (profiles/r02/ocean90/cg2d_geometry.txt).  Under __launch_bounds__(256) 3x4 has the
+// 512-register budget, keeps its overflow in AGPRs and has no scratch; 3x2 x 512 needs 212
+// VGPRs.  Both exceed their thread count on that grid's 3600 points and fit it only with
+// the all-land blocks left out (model.hip build_nbr); there 3x2 x 512 runs 1.40 and
+// 3x4 x 256 1.56 against 2x4 x 512's 1.62 us/iteration (profiles/r07/cg2d_compact/).
+// 3x2 x 512 leads the preference list; 3x4 x 256 fits no grid that 3x2 x 512 does not and is
+// reached through MGCM_CG2D_BXY only.  2x4 x 384 on the compacted grid gained 5.8 % of the
+// step against 3x2 x 512's 9.1 % and was removed after the A/B.
+static const CgxGeom CGX[] = {{2, 4, 512}, {2, 2, 1024}, {3, 4, 256}, {3, 2, 512}};
 constexpr int CGX_N = (int)(sizeof(CGX) / sizeof(CGX[0]));
 int cg2d_bxy_variants() { return CGX_N; }
 int cg2d_bxy_geometry(int v, int *bx, int *by, int *nt) {
@@ -1722,10 +1743,10 @@ int cg2d_bxy_geometry(int v, int *bx, int *by, int *nt) {
 template <int BX, int BY, int NT>
 static hipError_t launch_bxy_t(const Dims &d, const Params &p, const Fields &f, const unsigned *nbx, const int *blkx,
                                int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *slot2,
-                               const long *srcOf, hipStream_t s) {
+                               const long *srcOf, const int *dropG, int nDrop, int *guardHit, hipStream_t s) {
   if (nBlk > NT) return hipErrorInvalidValue;
   const bool mr = nIterMin >= 0, fm = p.cg2dUseFMA != 0, sr = p.useSRCGSolver != 0;
-  const size_t lds = (2 * ((size_t)BX * BY * NT + 1) + 4 * 16) * sizeof(double);
+  const size_t lds = (2 * ((size_t)BX * BY * NT + 1) + 4 * 16 + 2) * sizeof(double);
   auto kern = sr   ? (mr ? (fm ? k_cg2d_bxy<BX, BY, NT, true, true, true> : k_cg2d_bxy<BX, BY, NT, true, false, true>)
                          : (fm ? k_cg2d_bxy<BX, BY, NT, false, true, true>
                                : k_cg2d_bxy<BX, BY, NT, false, false, true>))
@@ -1739,18 +1760,22 @@ static hipError_t launch_bxy_t(const Dims &d, const Params &p, const Fields &f, 
     attrSet[ai] = true;
   }
   hipLaunchKernelGGL(kern, dim3(1), dim3(NT), lds, s, d, p, f, nbx, blkx, nBlk, maxIters, nIterMin, rec, stepCounter, slot2,
-                     srcOf);
+                     srcOf, dropG, nDrop, guardHit);
   return hipGetLastError();
 }
 // slot2 (or nullptr): the 2-D point -> LDS slot map of the fused EXCH(cg2d_x) + etaN epilogue
 hipError_t launch_cg2d_bxy(int v, const Dims &d, const Params &p, const Fields &f, const unsigned *nbx, const int *blkx,
                            int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *slot2,
-                           const long *srcOf, hipStream_t s) {
-#define CGX_CASE(V, BX, BY, NT) \
-  case V: return launch_bxy_t<BX, BY, NT>(d, p, f, nbx, blkx, nBlk, maxIters, nIterMin, rec, stepCounter, slot2, srcOf, s);
+                           const long *srcOf, const int *dropG, int nDrop, int *guardHit, hipStream_t s) {
+#define CGX_CASE(V, BX, BY, NT)                                                                                  \
+  case V:                                                                                                        \
+    return launch_bxy_t<BX, BY, NT>(d, p, f, nbx, blkx, nBlk, maxIters, nIterMin, rec, stepCounter, slot2, srcOf, dropG, \
+                                    nDrop, guardHit, s);
   switch (v) {
     CGX_CASE(0, 2, 4, 512)
     CGX_CASE(1, 2, 2, 1024)
+    CGX_CASE(2, 3, 4, 256)
+    CGX_CASE(3, 3, 2, 512)
   }
 #undef CGX_CASE
   return hipErrorInvalidValue;

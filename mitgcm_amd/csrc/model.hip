@@ -64,7 +64,7 @@ hipError_t launch_cg2d_block(const Dims &, const Params &, const Fields &, const
 int cg2d_block_ppt(int nPts);
 int cg2d_ref_max_points();
 hipError_t launch_cg2d_bxy(int, const Dims &, const Params &, const Fields &, const unsigned *, const int *, int, int,
-                           int, SolveRecord *, int *, const int *, const long *, hipStream_t);
+                           int, SolveRecord *, int *, const int *, const long *, const int *, int, int *, hipStream_t);
 int cg2d_bxy_geometry(int, int *, int *, int *);
 int cg2d_bxy_variants();
 hipError_t launch_cg2d_blk2(const Dims &, const Params &, const Fields &, const unsigned *, const int *, int, int, int,
@@ -232,6 +232,14 @@ struct mgcm_model {
   int nBlkX = 0;
   int bxyVar = -1;              // k_cg2d_bxy geometry (kernels_solve.hip CGX[])
   int *d_slot2 = nullptr;       // per 2-D point: k_cg2d_bxy's LDS slot of its value after EXCH, or -1
+  // land-block compaction of the k_cg2d_bxy tables (build_nbr): the 2-D offsets of the points
+  // of the all-land blocks left out, which the solver's prologue scans for a non-zero
+  std::vector<int> h_dropG;
+  int *d_dropG = nullptr;
+  int nDropBlk = 0;             // blocks left out (0: the tables cover the whole grid)
+  bool noCompact = false;       // set once the zero-on-land invariant was seen broken: full tables from then on
+  int *h_guard = nullptr;       // pinned host word the solver sets when its scan finds a non-zero
+  int *d_guard = nullptr;       // its device address
   bool latlonTopology = true;   // false once a custom halo map (e.g. EXCH2 cube) is installed
   // multi-workgroup CG2D (kernels_cg2d_mwg.hip): tables of every part, device buffers
   bool useMwg = false;
@@ -296,6 +304,7 @@ struct mgcm_model {
 };
 
 static void drop_graphs(mgcm_model *m);
+static int land_eta_check(mgcm_model *m, const char *name, const double *host, long n);
 
 static long field_count(const mgcm_model *m, FieldKind k) {
   if (k == F1D) return m->d.Nr + 1;
@@ -519,19 +528,120 @@ static int build_nbr(mgcm_model *m) {
   }
   // BX x BY blocks (k_cg2d_bxy), same global-index construction; the first geometry of
   // the preference list the grid tiles into
+  //
+  // Land-block compaction.  A block is left out of the tables when every point of it is a dry
+  // column with all four faces closed at every level -- decided from the static arrays
+  // INI_CG2D / UPDATE_CG2D build aW2d / aS2d from (h0FacW / h0FacS under the non-linear free
+  // surface, else hFacW / hFacS) and from hFacC.  Only the kept blocks are numbered; a left-out
+  // point's slot is the ZERO slot, so its neighbours read 0.0, and its slot2 is -1, so the
+  // fused epilogue keeps its global value.  This is exact, not approximate, while cg2d_b and
+  // the first guess cg2d_x are 0.0 on those points, which holds by induction over the steps:
+  //   * cg2d_b: sfp_rhs_column (common.h) sums the fluxes through the point's faces, all 0.0
+  //     with the faces closed, the fresh-water term, masked by maskInC (0 on a dry column),
+  //     and the free-surface term, a multiple of etaH (etaN without exactConserv);
+  //   * cg2d_x, the first guess, is Bo_surf*etaN there; after the solve the epilogue (or
+  //     k_exch_eta) sets etaN = recip_Bo*cg2d_x, 0.0 where cg2d_x stayed 0.0;
+  //   * etaH: UPDATE_ETAH (k_corr_cont, k_calc_r_star) adds the masked divergence of the
+  //     transports through the same closed faces to etaN: 0.0 again.
+  // So the invariant can only be broken from outside: eta loaded from the host (checked by
+  // mgcm_init and mgcm_put*, land_eta_check) or b / x handed to mgcm_cg2d.  The solver's
+  // prologue scans the left-out points on every solve and records numIters = -1 on a
+  // non-zero (k_cg2d_bxy), which mgcm_cg2d answers by solving again on the full tables and a
+  // step reports as an error: a broken invariant is never a silently different answer.
+  //
+  // Selection: the first geometry of the preference list that the grid tiles into and that
+  // fits its thread count -- with every block where the full count fits (tables as without
+  // compaction), with the all-land blocks left out only where the full count does not fit
+  // but the kept count does.  MGCM_CG2D_BXY=<BX>x<BY>x<NT> (or the variant's index) forces a
+  // geometry; MGCM_CG2D_COMPACT=0 never leaves blocks out, =1 leaves them out wherever there
+  // are any.  After a broken invariant (noCompact) neither switch applies: the full tables of
+  // the first two geometries, as before compaction existed.
   m->nBlkX = 0;
   int BX = 0, BY = 0, NT = 0, nBx = 0;
   m->bxyVar = -1;
+  m->h_dropG.clear();
+  m->nDropBlk = 0;
+  if (m->d_dropG) { (void)hipFree(m->d_dropG); m->d_dropG = nullptr; }
+  const char *envC = m->noCompact ? nullptr : getenv("MGCM_CG2D_COMPACT");
+  const int compactMode = m->noCompact ? 0 : (envC ? (atoi(envC) != 0 ? 2 : 0) : 1);   // 0 off, 1 where needed, 2 always
+  const bool blocked = m->latlonTopology && !getenv("MGCM_CG2D_NOBLOCKED");
+  // dry[global (J-1)*Nx + (I-1)]: the point may be left out
+  std::vector<char> dry;
+  auto gpt0 = [&](int I, int J, int &i, int &j, int &t) {
+    const int bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
+    t = bj * d.nSx + bi; i = (I - 1) % d.sNx + 1; j = (J - 1) % d.sNy + 1;
+  };
+  if (blocked && compactMode > 0) {
+    const bool nl = m->p.nonlinFreeSurf > 0;
+    const size_t n3 = (size_t)d.n3 * d.nTiles;
+    std::vector<double> hW(n3), hS(n3), hC(n3);
+    HIPCHK(hipMemcpy(hW.data(), nl ? m->f.h0FacW : m->f.hFacW, n3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hS.data(), nl ? m->f.h0FacS : m->f.hFacS, n3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hC.data(), nl ? m->f.h0FacC : m->f.hFacC, n3 * sizeof(double), hipMemcpyDeviceToHost));
+    dry.assign((size_t)Nx * Ny, 0);
+    for (int J = 1; J <= Ny; J++)
+      for (int I = 1; I <= Nx; I++) {
+        int i, j, t;
+        gpt0(I, J, i, j, t);
+        bool closed = true;
+        for (int k = 1; k <= d.Nr && closed; k++)
+          closed = hC[MG_I3(d, i, j, k, t)] == 0.0 && hW[MG_I3(d, i, j, k, t)] == 0.0 &&
+                   hW[MG_I3(d, i + 1, j, k, t)] == 0.0 && hS[MG_I3(d, i, j, k, t)] == 0.0 &&
+                   hS[MG_I3(d, i, j + 1, k, t)] == 0.0;
+        dry[(size_t)(J - 1) * Nx + (I - 1)] = closed;
+      }
+  }
+  auto blockDry = [&](int I0, int J0, int bx, int by) {
+    if (dry.empty()) return false;
+    for (int b = 0; b < by; b++)
+      for (int a = 0; a < bx; a++)
+        if (!dry[(size_t)(J0 + b - 1) * Nx + (I0 + a - 1)]) return false;
+    return true;
+  };
+  bool compacted = false;
   {
-    static const int pref[] = {0, 1};
+    // variants of kernels_solve.hip CGX[]: 3x2x512 first, the measured order (DESIGN.md "CG2D
+    // on one CU", profiles/r07/cg2d_compact/); 3x4x256 (variant 2) fits no grid that 3x2x512
+    // does not -- every 3x4 block is two 3x2 blocks -- and is reached by MGCM_CG2D_BXY only
+    static const int prefNew[] = {3, 0, 1}, prefOld[] = {0, 1};
+    std::vector<int> pref;
+    int forced = -1;
+    const char *envG = m->noCompact ? nullptr : getenv("MGCM_CG2D_BXY");
+    if (envG && *envG) {
+      int fx = 0, fy = 0, ft = 0;
+      if (sscanf(envG, "%dx%dx%d", &fx, &fy, &ft) == 3) {
+        for (int v = 0; v < cg2d_bxy_variants(); v++) {
+          int bx, by, nt;
+          cg2d_bxy_geometry(v, &bx, &by, &nt);
+          if (bx == fx && by == fy && nt == ft) forced = v;
+        }
+      } else if (envG[0] >= '0' && envG[0] <= '9' && atoi(envG) < cg2d_bxy_variants())
+        forced = atoi(envG);
+      if (forced < 0) return set_err("build_nbr: MGCM_CG2D_BXY=%s names no k_cg2d_bxy geometry", envG);
+      pref.push_back(forced);
+    } else if (m->noCompact)
+      pref.assign(prefOld, prefOld + sizeof(prefOld) / sizeof(int));
+    else
+      pref.assign(prefNew, prefNew + sizeof(prefNew) / sizeof(int));
     for (int v : pref) {
       int bx, by, nt;
       if (cg2d_bxy_geometry(v, &bx, &by, &nt)) continue;
       const int n = (Nx % bx == 0 && Ny % by == 0) ? (Nx / bx) * (Ny / by) : 0;
-      if (n > 0 && n <= nt) { m->bxyVar = v; BX = bx; BY = by; NT = nt; nBx = n; break; }
+      if (n == 0) continue;
+      int nDry = 0;
+      if (blocked && compactMode > 0)
+        for (int J0 = 1; J0 <= Ny; J0 += by)
+          for (int I0 = 1; I0 <= Nx; I0 += bx) nDry += blockDry(I0, J0, bx, by) ? 1 : 0;
+      if (n <= nt && !(compactMode == 2 && nDry > 0)) { m->bxyVar = v; BX = bx; BY = by; NT = nt; nBx = n; break; }
+      if (nDry > 0 && n - nDry > 0 && n - nDry <= nt) {
+        m->bxyVar = v; BX = bx; BY = by; NT = nt; nBx = n - nDry; compacted = true;
+        break;
+      }
     }
+    if (forced >= 0 && blocked && m->bxyVar < 0)
+      return set_err("build_nbr: the grid does not fit the k_cg2d_bxy geometry MGCM_CG2D_BXY=%s", envG);
   }
-  if (m->latlonTopology && m->bxyVar >= 0 && !getenv("MGCM_CG2D_NOBLOCKED")) {
+  if (blocked && m->bxyVar >= 0) {
     const int NPT = BX * BY, NB = 2 * (BX + BY);
     const unsigned Z = (unsigned)(NPT * NT);
     // LDS slot of an interior point: point-in-block major, block minor (p*NT + block),
@@ -540,13 +650,18 @@ static int build_nbr(mgcm_model *m) {
     {
       int qb = 0;
       for (int J0 = 1; J0 <= Ny; J0 += BY)
-        for (int I0 = 1; I0 <= Nx; I0 += BX, qb++)
+        for (int I0 = 1; I0 <= Nx; I0 += BX) {
+          const bool drop = compacted && blockDry(I0, J0, BX, BY);
           for (int b = 0; b < BY; b++)
             for (int a = 0; a < BX; a++) {
               const int I = I0 + a, J = J0 + b, bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
               const int t = bj * d.nSx + bi, i = (I - 1) % d.sNx + 1, j = (J - 1) % d.sNy + 1;
-              slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)] = (unsigned)((b * BX + a) * NT + qb);
+              if (drop) m->h_dropG.push_back((int)MG_I2(d, i, j, t));
+              else slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)] = (unsigned)((b * BX + a) * NT + qb);
             }
+          if (drop) m->nDropBlk++;
+          else qb++;
+        }
     }
     auto cmp = [&](long g) -> unsigned {
       unsigned c = compact(g);
@@ -565,7 +680,8 @@ static int build_nbr(mgcm_model *m) {
     std::vector<int> blkx((size_t)NPT * NT, (int)MG_I2(d, 1, 1, 0));
     int q = 0;
     for (int J0 = 1; J0 <= Ny; J0 += BY)
-      for (int I0 = 1; I0 <= Nx; I0 += BX, q++) {
+      for (int I0 = 1; I0 <= Nx; I0 += BX) {
+        if (compacted && blockDry(I0, J0, BX, BY)) continue;
         std::vector<int> ii(NPT), jj(NPT), tt(NPT);
         for (int b = 0; b < BY; b++)
           for (int a = 0; a < BX; a++) {
@@ -584,6 +700,7 @@ static int build_nbr(mgcm_model *m) {
           v[2 * BY + BX + a] = nbv(ii[no], jj[no] + 1, tt[no]);
         }
         for (int k = 0; k < NB / 2; k++) nbx[(size_t)(NB / 2) * q + k] = v[2 * k] | (v[2 * k + 1] << 16);
+        q++;
       }
     // the epilogue's EXCH_XY_RL(cg2d_x): every 2-D point's value is the slot of itself
     // (interior) or of its interior source (halo), -1 where neither (kept as it is)
@@ -592,7 +709,8 @@ static int build_nbr(mgcm_model *m) {
       for (int I = 1; I <= Nx; I++) {
         int i, j, t;
         gpt(I, J, i, j, t);
-        slot2[(size_t)MG_I2(d, i, j, t)] = (int)slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)];
+        const unsigned sl = slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)];
+        slot2[(size_t)MG_I2(d, i, j, t)] = sl == Z ? -1 : (int)sl;   // -1: a point of a left-out block
       }
     for (size_t g = 0; g < slot2.size(); g++)
       if (srcOf[g] >= 0) slot2[g] = slot2[(size_t)srcOf[g]];
@@ -606,6 +724,15 @@ static int build_nbr(mgcm_model *m) {
     HIPCHK(hipMalloc(&m->d_blkx, blkx.size() * sizeof(int)));
     HIPCHK(hipMemcpy(m->d_blkx, blkx.data(), blkx.size() * sizeof(int), hipMemcpyHostToDevice));
     m->nBlkX = nBx;
+    if (!m->h_dropG.empty()) {
+      HIPCHK(hipMalloc(&m->d_dropG, m->h_dropG.size() * sizeof(int)));
+      HIPCHK(hipMemcpy(m->d_dropG, m->h_dropG.data(), m->h_dropG.size() * sizeof(int), hipMemcpyHostToDevice));
+      if (!m->h_guard) {
+        HIPCHK(hipHostMalloc((void **)&m->h_guard, 64, hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer((void **)&m->d_guard, m->h_guard, 0));
+      }
+      *m->h_guard = 0;
+    }
   }
   return 0;
 }
@@ -920,6 +1047,8 @@ void mgcm_destroy(mgcm_model *m) {
   if (m->d_nbx) hipFree(m->d_nbx);
   if (m->d_blkx) hipFree(m->d_blkx);
   if (m->d_slot2) hipFree(m->d_slot2);
+  if (m->d_dropG) hipFree(m->d_dropG);
+  if (m->h_guard) hipHostFree(m->h_guard);
   if (m->d_ctr) hipFree(m->d_ctr);
   for (auto &q : m->exchBuf)
     if (q) hipFree(q);
@@ -1020,6 +1149,7 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
   if (!strcmp(name, "ovlMsOn")) return m->ovlMs[1];
   if (!strcmp(name, "ovlMsOff")) return m->ovlMs[0];
   if (!strcmp(name, "cg2dBxyVariant")) return (double)m->bxyVar;
+  if (!strcmp(name, "cg2dDroppedBlocks")) return (double)(m->nBlkX > 0 ? m->nDropBlk : 0);
   // the launch layout of the last FORWARD_STEP built (one_step): bit 0 THERMODYNAMICS folded
   // into DYNAMICS' grids (k_dt_l1/l2/l3), 1 DO_OCEANIC_PHYS + CALC_PHI_HYD in one pass,
   // 2 the tracers on the second stream, 3 joined only before the correction step
@@ -1040,6 +1170,7 @@ int mgcm_put(mgcm_model *m, const char *name, const double *host, long count) {
   if (!fd) return set_err("mgcm_put: unknown field %s", name);
   const long n = field_count(m, fd->kind);
   if (count > n || count <= 0) return set_err("mgcm_put: %s count %ld > %ld", name, count, n);
+  if (m->ready && land_eta_check(m, name, host, count)) return -1;
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(mg_host_copy(field_ptr(m, fd), host, count * sizeof(double), hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
@@ -1077,6 +1208,7 @@ int mgcm_put_batch_async(mgcm_model *m, int n, const char *const *names, const d
     const long lim = field_count(m, fd->kind);
     if (counts[i] > lim || counts[i] <= 0)
       return set_err("mgcm_put_batch_async: %s count %ld > %ld", names[i], counts[i], lim);
+    if (m->ready && land_eta_check(m, names[i], hosts[i], counts[i])) return -1;
     dst[i] = field_ptr(m, fd);
     total += counts[i];
     maxc = std::max(maxc, counts[i]);
@@ -1249,7 +1381,19 @@ int mgcm_init(mgcm_model *m) {
     m->allocs.push_back(m->snapH);
   }
   if (upload_halo(m)) return -1;
+  m->noCompact = false;
   if (build_nbr(m)) return -1;
+  if (!m->h_dropG.empty()) {
+    // the state the fields were loaded with (a cold start, a pickup): eta must be 0.0 on the
+    // points the compacted tables leave out, else the full tables (build_nbr)
+    const long n2a = m->d.n2 * m->d.nTiles;
+    std::vector<double> eta((size_t)n2a);
+    for (const char *nm : {"etaN", "etaH"}) {
+      if (!strcmp(nm, "etaH") && m->p.nIter0 == 0) continue;   // INI_PSURF below: etaH = etaN
+      HIPCHK(hipMemcpy(eta.data(), !strcmp(nm, "etaN") ? m->f.etaN : m->f.etaH, n2a * sizeof(double), hipMemcpyDeviceToHost));
+      if (land_eta_check(m, nm, eta.data(), n2a)) return -1;
+    }
+  }
   // CG2D kernel: the single-workgroup blocked solvers on lat-lon grids that tile into their
   // blocks; otherwise the multi-workgroup solver (the generic single-workgroup kernel measured
   // 12.7 against 4.2 us/iteration on the cube, round 3)
@@ -1386,12 +1530,44 @@ static hipError_t launch_cg2d(mgcm_model *m, int maxIters, int nIterMin, bool fu
   }
   if (m->nBlkX > 0)
     return launch_cg2d_bxy(m->bxyVar, m->d, m->p, m->f, m->d_nbx, m->d_blkx, m->nBlkX, maxIters, nIterMin, m->d_rec,
-                           m->d_ctr + 1, fuseEta ? m->d_slot2 : nullptr, m->d_srcOf, m->stream);
+                           m->d_ctr + 1, fuseEta ? m->d_slot2 : nullptr, m->d_srcOf, m->d_dropG, (int)m->h_dropG.size(),
+                           m->h_dropG.empty() ? nullptr : m->d_guard, m->stream);
   if (m->nBlk > 0)
     return launch_cg2d_blk2(m->d, m->p, m->f, m->d_nb4, m->d_blk, m->nBlk, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
                             m->stream);
   return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
                            m->stream);
+}
+
+// The zero-on-land invariant of the compacted k_cg2d_bxy tables (build_nbr), on the host side.
+// land_uncompact: the full tables of the geometry used before compaction existed, from now on;
+// the captured graphs hold the old tables' addresses and go.
+static int land_uncompact(mgcm_model *m) {
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  drop_graphs(m);
+  m->noCompact = true;
+  if (build_nbr(m)) return -1;
+  if (m->h_guard) *m->h_guard = 0;
+  if (m->nBlkX == 0 && m->nBlk == 0 && !m->p.cg2dRefOrder && !m->useMwg)
+    return set_err("land_uncompact: no single-workgroup CG2D fits this grid without leaving the all-land blocks out");
+  return 0;
+}
+// eta arriving from the host (n values of a 2-D field from its start): non-zero on a left-out point?
+static int land_eta_check(mgcm_model *m, const char *name, const double *host, long n) {
+  if (m->h_dropG.empty() || (strcmp(name, "etaN") && strcmp(name, "etaH"))) return 0;
+  for (int g : m->h_dropG)
+    if (g < n && !(host[g] == 0.0)) return land_uncompact(m);
+  return 0;
+}
+// a step's solve found a non-zero on a left-out point (k_cg2d_bxy's guard): its results are
+// not those of the full solve, and every later call says so
+static int land_guard_check(mgcm_model *m, const char *who) {
+  if (m->h_guard && *(volatile int *)m->h_guard)
+    return set_err("%s: a CG2D solve of an earlier step found a non-zero cg2d_b or cg2d_x on a land point of a block left "
+                   "out of the solver's tables (recorded as numIters = -1); its results are invalid -- load the state "
+                   "through mgcm_put / mgcm_init, which check eta on those points, or set MGCM_CG2D_COMPACT=0", who);
+  return 0;
 }
 
 static int check_ready(mgcm_model *m) {
@@ -1998,6 +2174,7 @@ static int ovl_trial(mgcm_model *m) {
 
 int mgcm_forward_step(mgcm_model *m, int nsteps) {
   if (check_ready(m)) return -1;
+  if (land_guard_check(m, "mgcm_forward_step")) return -1;
   if (nsteps <= 0 || nsteps > m->maxRec) return set_err("mgcm_forward_step: nsteps %d out of range", nsteps);
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipMemsetAsync(m->d_ctr + 1, 0, sizeof(int), m->stream));
@@ -2505,7 +2682,7 @@ int mgcm_sync(mgcm_model *m) {
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipStreamSynchronize(m->stream));
   ev_collect(m);
-  return 0;
+  return land_guard_check(m, "mgcm_sync");
 }
 
 int mgcm_solve_stats(mgcm_model *m, int back, double *firstResidual, double *lastResidual, int *numIters,
@@ -2693,9 +2870,20 @@ int mgcm_cg2d(mgcm_model *m, double *cg2d_b, double *cg2d_x, double *firstResidu
   ev_end(m, K_CG2D, ev);
   m->p.useSRCGSolver = sr;
   HIPCHK(le);
+  SolveRecord r;
+  if (!m->h_dropG.empty()) {
+    // compacted tables: the record first, before the caller's arrays are overwritten.  A
+    // solve the kernel's guard marked failed had a non-zero b or first guess on a point of a
+    // left-out all-land block: the full tables from now on, and the same solve again
+    HIPCHK(hipMemcpyAsync(&r, m->d_rec, sizeof r, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    if (r.numIters == -1) {
+      if (land_uncompact(m)) return -1;
+      return mgcm_cg2d(m, cg2d_b, cg2d_x, firstResidual, minResidualSq, lastResidual, numIters, nIterMin);
+    }
+  }
   HIPCHK(mg_host_copy(cg2d_b, m->f.cg2d_b, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
   HIPCHK(mg_host_copy(cg2d_x, m->f.cg2d_x, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-  SolveRecord r;
   HIPCHK(hipMemcpyAsync(&r, m->d_rec, sizeof r, hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   *firstResidual = r.firstResidual;

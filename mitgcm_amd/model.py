@@ -125,6 +125,11 @@ class Model:
         a = np.ascontiguousarray(arr, dtype=np.float64)
         check(lib().mgcm_put(self.h, name.encode(), _dp(a), a.size), "mgcm_put(%s)" % name)
 
+    def set(self, name, arr):
+        """put() on an initialised model: state set from the host between steps.  etaN / etaH
+        are checked against the CG2D tables' left-out land blocks (model.hip land_eta_check)."""
+        self.put(name, arr)
+
     def get(self, name):
         a = np.zeros(self._shape(name))
         check(lib().mgcm_get(self.h, name.encode(), _dp(a), a.size), "mgcm_get(%s)" % name)
