@@ -416,6 +416,11 @@ struct MwgTables {
   unsigned long long *xs;     // [2 buffers][exported points][2] q = M r (CG2D_SR: r, q, v) of the points
                               // other parts' rings hold (the standard solve uses buffer 0 only)
   size_t hsBytes;
+  // cg2dRefOrder (k_cg2d_mwg<.., REF>): the sums in the reference's order, whole-domain tables only
+  int ref;                // 1: reference-order sums (per tile sequential, then tile order)
+  int nTiles;             // tiles of the domain (ref)
+  const int *ownN;        // [G] owned points of the part: slots 0 .. ownN-1, (j outer, i inner) of its strip
+  unsigned long long *refc;   // [2 parities][3 values][G carries, then nTiles tile partials][2] (ref; behind xs)
 };
 
 // MONITOR dynstat on the device (kernels_monitor.hip): one field's arrays; arr3d / hf3d:

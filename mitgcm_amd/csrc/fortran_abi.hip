@@ -1337,7 +1337,10 @@ void mgcm_amd_init_(const int *myIter) {
   model("MGCM_AMD_INIT");
   install_fault_report();
   // device options with no PARAMS.h counterpart, from the environment:
-  // MGCM_CG2D_REFORDER=1 sums CG2D in the reference's order (cg2dRefOrder, parity runs)
+  // MGCM_CG2D_REFORDER=1 sums CG2D in the reference's order (cg2dRefOrder, parity runs); past
+  // one workgroup's points (the cs32 and llc30 layouts) that is the multi-workgroup solver's
+  // reference-order form, which runs on one device model only: with several models
+  // mgcm_set_tile_range refuses it in setup_shards
   // (several models: each is set up on the whole domain -- the CG2D tables too -- and only
   // then restricted to its tiles, setup_shards)
   free_links();

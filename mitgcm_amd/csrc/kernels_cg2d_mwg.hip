@@ -32,6 +32,16 @@
 // tiles: thread partials (OPT terms in order) -> pairwise tree over the NT threads -> per
 // workgroup partial; lane l of every wave adds partials l, l+64, ... in order, then the
 // pairwise tree over the 64 lanes.  mgcm_cg2d_sum_plan exports it for the oracle.
+//
+// cg2dRefOrder (k_cg2d_mwg<.., REF = true>, "mwg_ref"): the same solve with every sum in the
+// reference's own order -- each tile sequentially, j outer and i inner, from 0.0
+// (cg2d.F:211-243, 268-296, 305-337), the tile partials in tile order from 0.0
+// (global_sum_tile.F:161-191).  A part's owned slots are its strip's points in that order, so
+// a tile's sum is the chain of its parts' slot-ordered terms: each part adds its terms to the
+// carry its predecessor in the tile published and hands the result on; the tile's last part
+// publishes the tile partial, and every part adds the nTiles partials itself (mw_sync_ref).
+// Two hand-offs per iteration as above, the same granules, tags and double buffering; no tree,
+// no DPP in any sum.  The parity mode: a chain costs sNx*sNy dependent adds per sum.
 #include "common.h"
 
 namespace mgcm {
@@ -164,6 +174,25 @@ struct MwImport {
   const gu64 *src; // the export granules read (T.xs; CG2D_SR alternates two buffers)
 };
 
+// the import sweep of the waves other than wave 0 (threads 64 .. NT-1)
+template <bool SYS>
+__device__ __forceinline__ void mw_import_sweep(const MwImport &imp, const MwgTables &T, unsigned tag, unsigned ep) {
+  const int tid = threadIdx.x;
+  for (int q0 = 0; q0 < imp.nImp; q0 += MW_NT - 64) {
+    const int qq = q0 + tid - 64;
+    const bool act = qq < imp.nImp;
+    gu64 *src = (gu64 *)imp.src + (size_t)2 * (act ? T.impC[imp.gi + qq] : 0);
+    double xv = 0.0;
+    unsigned spins = 0;
+    for (;;) {
+      const bool good = !act || gran_get<SYS>(src, tag, xv);
+      if (__all(good)) break;
+      if (spin_fail<SYS>(spins, (gu32 *)T.ctr + 1, ep)) break;   // the timeout word fails the solve
+    }
+    if (act) imp.imp_l[qq] = xv;
+  }
+}
+
 template <int NV, bool MAXOP, bool SYS = false>
 __device__ __forceinline__ bool mw_sync(double *v, const MwgTables &T, int g, int &nsync, double *red, unsigned ep,
                                         const MwImport *imp = nullptr) {
@@ -244,19 +273,92 @@ __device__ __forceinline__ bool mw_sync(double *v, const MwgTables &T, int g, in
     }
     if (lane == 0) red[15 * 16] = ok ? 1.0 : 0.0;
   } else if (imp) {
-    for (int q0 = 0; q0 < imp->nImp; q0 += MW_NT - 64) {
-      const int qq = q0 + tid - 64;
-      const bool act = qq < imp->nImp;
-      gu64 *src = (gu64 *)imp->src + (size_t)2 * (act ? T.impC[imp->gi + qq] : 0);
-      double xv = 0.0;
-      unsigned spins = 0;
+    mw_import_sweep<SYS>(*imp, T, tag, ep);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NV; q++) v[q] = red[(8 + q) * 16];
+  return red[15 * 16] != 0.0;
+}
+
+// One grid-wide reduction of NV sums in the reference's order (cg2dRefOrder): tv[q][m] is the
+// term of sum q at this thread's owned point m (slot m*NT + tid; 0.0 on a padding slot).
+//   1. The terms go to LDS at their slot, the NV sums of a slot side by side.
+//   2. Lane q < NV of wave 0 walks the part's ownN real points in slot order, e = e + term,
+//      from +0.0 in a tile's first part, else from the carry granule of the tile's previous
+//      part (awaited first), and publishes e: the carry of part g, or from the tile's last part
+//      the tile partial.  The NV chains run side by side in one wave.
+//   3. Wave 0 of every part reads the nTiles tile partials, 64 per sweep (one per lane, each
+//      sweep repeated until its granules carry this phase's tag), and every lane adds them in
+//      tile order from 0.0 (v_readlane of lane 0, 1, ...): the identical value in every part,
+//      for any nTiles.  The other waves sweep the ring imports meanwhile, as in mw_sync.
+// Granules: T.refc[nsync & 1][q][G carries, then nTiles partials], tagged mw_tag(ep, nsync).
+// Two buffers suffice, by the argument of the file header: a part finishes reduction n only
+// after reading every tile partial of n; tile t's partial is published by t's last part, which
+// first needed the carry of its predecessor, and so on down to t's first part -- so by then
+// EVERY part has published into reduction n, hence has finished reading reduction n - 1 (its
+// loads of n - 1 returned before it left that reduction).  A part that runs ahead into
+// reduction n + 1 therefore overwrites granules of n - 1 that nobody reads any more, and no
+// part can reach n + 2 before the slowest has published into n + 1.  Every wait is bounded by
+// spin_fail: a timeout fails the solve (numIters = -1) in every part.
+template <int NV>
+__device__ __forceinline__ bool mw_sync_ref(const double (&tv)[NV][MW_OPT], double *v, const MwgTables &T, int g,
+                                            int &nsync, double *red, double *term_l, unsigned ep,
+                                            const MwImport *imp = nullptr) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  nsync++;
+  const unsigned tag = mw_tag(ep, nsync);
+  const int nC = T.G + T.nTiles;
+  gu64 *C = (gu64 *)(T.refc + (size_t)(nsync & 1) * MW_NV * nC * 2);
+#pragma unroll
+  for (int m = 0; m < MW_OPT; m++)
+#pragma unroll
+    for (int q = 0; q < NV; q++) term_l[(m * MW_NT + tid) * NV + q] = tv[q][m];
+  __syncthreads();
+  if (wv == 0) {
+    const int tile = g / T.partsPerTile, pos = g % T.partsPerTile, nOwn = T.ownN[g];
+    const bool mine = lane < NV;
+    gu64 *Cq = C + (size_t)(mine ? lane : 0) * nC * 2;
+    gu32 *tmo = (gu32 *)T.ctr + 1;
+    unsigned spins = 0;
+    bool ok = true;
+    double e = 0.0;
+    if (pos > 0)
       for (;;) {
-        const bool good = !act || gran_get<SYS>(src, tag, xv);
+        const bool good = !mine || gran_get(Cq + (size_t)(g - 1) * 2, tag, e);
         if (__all(good)) break;
-        if (spin_fail<SYS>(spins, (gu32 *)T.ctr + 1, ep)) break;   // the timeout word fails the solve
+        if (spin_fail(spins, tmo, ep)) { ok = false; break; }
       }
-      if (act) imp->imp_l[qq] = xv;
+    if (mine) {
+      for (int n = 0; n < nOwn; n++) e = e + term_l[n * NV + lane];
+      gran_put(Cq + (size_t)(pos == T.partsPerTile - 1 ? T.G + tile : g) * 2, tag, e);
     }
+    double acc[NV];
+#pragma unroll
+    for (int q = 0; q < NV; q++) acc[q] = 0.0;
+    for (int c0 = 0; ok && c0 < T.nTiles; c0 += 64) {
+      const bool act = c0 + lane < T.nTiles;
+      gu64 *src = C + (size_t)(T.G + (act ? c0 + lane : 0)) * 2;
+      double xv[NV];
+      for (;;) {
+        bool good = true;
+#pragma unroll
+        for (int q = 0; q < NV; q++) good = gran_get(src + (size_t)q * nC * 2, tag, xv[q]) && good;
+        if (__all(good || !act)) break;
+        if (spin_fail(spins, tmo, ep)) { ok = false; break; }
+      }
+      const int nl = T.nTiles - c0 < 64 ? T.nTiles - c0 : 64;
+      for (int l = 0; l < nl; l++)
+#pragma unroll
+        for (int q = 0; q < NV; q++) acc[q] = acc[q] + mw_lane(xv[q], l);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < NV; q++) red[(8 + q) * 16] = acc[q];
+      red[15 * 16] = ok ? 1.0 : 0.0;
+    }
+  } else if (imp) {
+    mw_import_sweep<false>(*imp, T, tag, ep);
   }
   __syncthreads();
 #pragma unroll
@@ -283,7 +385,8 @@ __device__ __forceinline__ bool mw_sync(double *v, const MwgTables &T, int g, in
 // g0, gN: this launch runs parts g0 .. g0+gN-1 of the T.G (all of them in one process; a
 // process's tiles' parts in the tile-sharded device CG2D, whose other parts run in the other
 // processes' launches on the same hand-off block)
-template <bool PINNED, bool SYS>
+// REF: the sums in the reference's order (mw_sync_ref; cg2dRefOrder on whole-domain tables, one process)
+template <bool PINNED, bool SYS, bool REF = false>
 __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, MwgTables T, int maxIters,
                                                     int nIterMinIn, SolveRecord *rec, int *stepCounter, int g0, int gN) {
   int g = (int)blockIdx.x;
@@ -300,6 +403,7 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
   double *r_l = lds + (SZ + 1);   // NO + NR used, + ZERO at SZ
   double *red = lds + 2 * (SZ + 1);   // 16 x 16 scratch
   double *imp_l = red + 16 * 16;      // IMAX: the ring q handed off at the last reduction
+  double *term_l = imp_l + T.IMAX;    // REF: MW_NV * NO per-point terms of the sums (no CG2D_SR there)
   const int tid = threadIdx.x;
   int nsync = 0;
   const unsigned ep = __hip_atomic_load((gu32 *)T.epoch, RLX_AGENT);
@@ -347,7 +451,7 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
     rb[m] = act ? f.cg2d_b[gg] : 0.0;
   }
   // CG2D_SR forms y = M r on ring 1 too: the ring points' preconditioner rows
-  const bool SR = p.useSRCGSolver != 0;
+  const bool SR = !REF && p.useSRCGSolver != 0;
   double rpC[MW_RPT], rpW0[MW_RPT], rpW1[MW_RPT], rpS0[MW_RPT], rpS1[MW_RPT];
 #pragma unroll
   for (int m = 0; m < MW_RPT; m++) {
@@ -395,12 +499,15 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
   __syncthreads();
   // cg2d.F:139-180: r = b - A x on owned points and ring 1
   double v3[3] = {0.0, 0.0, 0.0};
+  double t3[3][MW_OPT], t2[2][MW_OPT], t1[1][MW_OPT];   // REF: the per-point terms of the sums
 #pragma unroll
   for (int m = 0; m < MW_OPT; m++) {
     r[m] = b[m] - (aW0[m] * s_l[LO(nwe[m])] + aW1[m] * s_l[HI(nwe[m])] + aS0[m] * s_l[LO(nsn[m])] +
                    aS1[m] * s_l[HI(nsn[m])] + aC[m] * x[m]);
     v3[0] = v3[0] + r[m] * r[m];
     v3[1] = v3[1] + b[m];
+    t3[0][m] = r[m] * r[m];
+    t3[1][m] = b[m];
   }
 #pragma unroll
   for (int m = 0; m < MW_RPT; m++)
@@ -564,10 +671,12 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
       q[m] = pC[m] * r[m] + pW0[m] * r_l[LO(nwe[m])] + pW1[m] * r_l[HI(nwe[m])] + pS0[m] * r_l[LO(nsn[m])] +
              pS1[m] * r_l[HI(nsn[m])];
       v3[2] = v3[2] + q[m] * r[m];
+      t3[2][m] = q[m] * r[m];
       if ((exp >> m) & 1u) gran_put<SYS>(xs + (size_t)2 * T.ownC[go + m * MW_NT + tid], mw_tag(ep, nsync + 1), q[m]);
     }
     for (int qq = tid; qq < nImp; qq += MW_NT) s_l[NO + qq] = 0.0;
-    ok = ok && mw_sync<3, false, SYS>(v3, T, g, nsync, red, ep, &imp);
+    ok = ok && (REF ? mw_sync_ref<3>(t3, v3, T, g, nsync, red, term_l, ep, &imp)
+                    : mw_sync<3, false, SYS>(v3, T, g, nsync, red, ep, &imp));
     err_sq = v3[0];
     sumRHS = v3[1];
     double eta_qrN = v3[2], eta_qrNM1 = 1.0;
@@ -601,6 +710,7 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
           q[m] = aW0[m] * s_l[LO(nwe[m])] + aW1[m] * s_l[HI(nwe[m])] + aS0[m] * s_l[LO(nsn[m])] + aS1[m] * s_l[HI(nsn[m])] +
                  aC[m] * s[m];
           av[0] = av[0] + s[m] * q[m];
+          t1[0][m] = s[m] * q[m];
         }
         double rq[MW_RPT];
   #pragma unroll
@@ -608,7 +718,7 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
           rq[m] = raW0[m] * s_l[LO(rwe[m])] + raW1[m] * s_l[HI(rwe[m])] + raS0[m] * s_l[LO(rsn[m])] +
                   raS1[m] * s_l[HI(rsn[m])] + raC[m] * s_l[NO + m * MW_NT + tid];
         MW_STAMP(2);
-        ok = mw_sync<1, false, SYS>(av, T, g, nsync, red, ep);
+        ok = REF ? mw_sync_ref<1>(t1, av, T, g, nsync, red, term_l, ep) : mw_sync<1, false, SYS>(av, T, g, nsync, red, ep);
         MW_STAMP(3);
         if (!ok) break;
         const double alpha = eta_qrN / av[0];
@@ -619,6 +729,7 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
           x[m] = x[m] + alpha * s[m];
           r[m] = r[m] - alpha * q[m];
           v2[0] = v2[0] + r[m] * r[m];
+          t2[0][m] = r[m] * r[m];
           r_l[m * MW_NT + tid] = r[m];
         }
   #pragma unroll
@@ -633,10 +744,12 @@ __global__ void __launch_bounds__(MW_NT) k_cg2d_mwg(Dims d, Params p, Fields f, 
           q[m] = pC[m] * r[m] + pW0[m] * r_l[LO(nwe[m])] + pW1[m] * r_l[HI(nwe[m])] + pS0[m] * r_l[LO(nsn[m])] +
                  pS1[m] * r_l[HI(nsn[m])];
           v2[1] = v2[1] + q[m] * r[m];
+          t2[1][m] = q[m] * r[m];
           if ((exp >> m) & 1u) gran_put<SYS>(xs + (size_t)2 * T.ownC[go + m * MW_NT + tid], mw_tag(ep, nsync + 1), q[m]);
         }
         MW_STAMP(4);
-        ok = mw_sync<2, false, SYS>(v2, T, g, nsync, red, ep, &imp);
+        ok = REF ? mw_sync_ref<2>(t2, v2, T, g, nsync, red, term_l, ep, &imp)
+                 : mw_sync<2, false, SYS>(v2, T, g, nsync, red, ep, &imp);
         MW_STAMP(5);
         if (!ok) break;
         err_sq = v2[0];
@@ -694,16 +807,23 @@ hipError_t launch_cg2d_mwg(const Dims &d, const Params &p, const Fields &f, cons
   if (maxIters < 0 || maxIters > 30000) return hipErrorInvalidValue;
   if (gN < 0) { g0 = 0; gN = T.G; }
   if (g0 < 0 || gN < 1 || g0 + gN > T.G) return hipErrorInvalidValue;
+  // the reference-order sums chain the parts of every tile and add every tile's partial: the
+  // whole domain in one launch, one process, no CG2D_SR (mgcm_init and the entry points refuse
+  // the rest with a message)
+  const bool ref = T.ref != 0;
+  if (ref && (gN != T.G || T.sys || T.partsPerTile <= 0 || p.useSRCGSolver)) return hipErrorInvalidValue;
   hipError_t e = hipSuccess;
   size_t lds = (size_t)(2 * (T.SZ + 1) + 16 * 16 + (p.useSRCGSolver ? 2 : 1) * T.IMAX) * sizeof(double);
+  if (ref) lds += (size_t)MW_NV * MW_OPT * MW_NT * sizeof(double);   // the per-point terms
   // a part may claim its CU's whole LDS so that no other kernel's workgroup shares the CU
   // (THERMODYNAMICS running beside the solve, model.hip one_step)
   if (T.exclusive) lds = 160 * 1024;
   const bool pinned = T.pinned && !T.sys && gN == T.G;
-  const int v = (pinned ? 1 : 0) + (T.sys ? 2 : 0);
-  auto kern = v == 3 ? k_cg2d_mwg<true, true> : v == 2 ? k_cg2d_mwg<false, true>
+  const int v = ref ? 4 + (pinned ? 1 : 0) : (pinned ? 1 : 0) + (T.sys ? 2 : 0);
+  auto kern = v == 5 ? k_cg2d_mwg<true, false, true> : v == 4 ? k_cg2d_mwg<false, false, true>
+            : v == 3 ? k_cg2d_mwg<true, true> : v == 2 ? k_cg2d_mwg<false, true>
             : v == 1 ? k_cg2d_mwg<true, false> : k_cg2d_mwg<false, false>;
-  static bool attrSet[4] = {false, false, false, false};
+  static bool attrSet[6] = {false, false, false, false, false, false};
   if (!attrSet[v]) {
     e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;

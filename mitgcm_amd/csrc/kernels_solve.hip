@@ -1664,7 +1664,9 @@ int cg2d_block_ppt(int nPts) {
 size_t cg2d_block_lds_bytes(int ppt) { return (size_t)(2 * (ppt * CG_THREADS + 1) + 4 * CG_WAVES) * sizeof(double); }
 int cg2d_block_max_points() { return 8 * CG_THREADS; }  // LDS: 2*8193*8 B = 128 KiB
 
-// cg2dRefOrder: the reference-order sums need NP + nTiles more doubles of LDS (PPT <= 4)
+// cg2dRefOrder: the reference-order sums need NP + nTiles more doubles of LDS (PPT <= 4); a
+// grid with more points takes the multi-workgroup solver's reference-order form
+// (k_cg2d_mwg<.., REF>, kernels_cg2d_mwg.hip), so this is the threshold between the two
 int cg2d_ref_max_points() { return 4 * CG_THREADS; }
 static hipError_t launch_cg2d_ref(const Dims &d, const Params &p, const Fields &f, const unsigned *nbr, const int *gofs,
                                   int nPts, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter,

@@ -823,7 +823,7 @@ static int build_mwg(mgcm_model *m) {
   std::vector<unsigned> ownNb((size_t)G * NO * 2, (unsigned)SZ | ((unsigned)SZ << 16)), ringNb((size_t)G * NR * 2,
                                                                                                  (unsigned)SZ | ((unsigned)SZ << 16));
   std::vector<unsigned> ownExp((size_t)G * NT, 0u);
-  std::vector<int> impC((size_t)G * IMAX, 0), impG((size_t)G * IMAX, (int)MG_I2(d, 1, 1, d.t0)), nImp(G);
+  std::vector<int> impC((size_t)G * IMAX, 0), impG((size_t)G * IMAX, (int)MG_I2(d, 1, 1, d.t0)), nImp(G), ownN(G);
   m->mwgPlan.assign((size_t)G * NO, -1);
   // the exported points, numbered: their granules in the hand-off block
   std::vector<int> expSlot(exported.size(), -1);
@@ -832,6 +832,7 @@ static int build_mwg(mgcm_model *m) {
     if (exported[c]) expSlot[c] = nExp++;
   for (int g = 0; g < G; g++) {
     std::map<int, int> slot;
+    ownN[g] = (int)own[g].size();
     for (size_t n = 0; n < own[g].size(); n++) {
       const int p = (int)n / NT, tid = (int)n % NT;
       slot[own[g][n]] = p * NT + tid;
@@ -876,17 +877,26 @@ static int build_mwg(mgcm_model *m) {
   T = MwgTables{};
   if (mwg_upload(m, ownG, &T.ownG) || mwg_upload(m, ownC, &T.ownC) || mwg_upload(m, ownNb, &T.ownNb) ||
       mwg_upload(m, ownExp, &T.ownExp) || mwg_upload(m, ringG, &T.ringG) || mwg_upload(m, ringNb, &T.ringNb) ||
-      mwg_upload(m, impC, &T.impC) || mwg_upload(m, impG, &T.impG) || mwg_upload(m, nImp, &T.nImp))
+      mwg_upload(m, impC, &T.impC) || mwg_upload(m, impG, &T.impG) || mwg_upload(m, nImp, &T.nImp) ||
+      mwg_upload(m, ownN, &T.ownN))
     return -1;
   T.G = G; T.IMAX = IMAX; T.SZ = SZ; T.nExp = nExp;
   T.pinned = (G <= 32 && !getenv("MGCM_CG2D_SPREAD")) ? 1 : 0;
   T.sys = 0;
   T.exclusive = 0;
   T.partsPerTile = (d.t0 == 0 && d.nT == d.nTiles) ? nPartsTile : 0;   // part ranges: whole-domain tables only
+  // cg2dRefOrder: the sums chained along each tile's parts, then over the tiles (k_cg2d_mwg<.., REF>)
+  T.ref = m->p.cg2dRefOrder ? 1 : 0;
+  T.nTiles = d.nTiles;
+  if (T.ref && T.partsPerTile <= 0)
+    return set_err("mgcm_init: cg2dRefOrder in the multi-workgroup CG2D needs the whole domain's tiles, not the tile "
+                   "range [%d, %d) of %d (mgcm_set_tile_range)", d.t0, d.t0 + d.nT, d.nTiles);
   // hand-off block: 64 B of words (launch epoch, timeout word), the partial granules, the
-  // export granules; zeroed once here -- granule tags carry the launch epoch, so a launch
+  // export granules, with cg2dRefOrder the carry and tile-partial granules (2 buffers x 3 values
+  // x (G + nTiles) doubles); zeroed once here -- granule tags carry the launch epoch, so a launch
   // never matches an earlier launch's granules (a multiple of 16 B from the start)
-  const size_t partGr = (size_t)2 * 3 * G * 2, hs = 64 + (partGr + (size_t)nExp * 4) * sizeof(unsigned long long);
+  const size_t partGr = (size_t)2 * 3 * G * 2, refGr = T.ref ? (size_t)2 * 3 * (G + d.nTiles) * 2 : 0;
+  const size_t hs = 64 + (partGr + (size_t)nExp * 4 + refGr) * sizeof(unsigned long long);
   char *blk = nullptr;
   HIPCHK(hipMalloc(&blk, hs));
   HIPCHK(hipMemset(blk, 0, hs));
@@ -901,6 +911,7 @@ static int build_mwg(mgcm_model *m) {
   T.ctr = (unsigned *)blk;
   T.part = (unsigned long long *)(blk + 64);
   T.xs = T.part + partGr;
+  T.refc = T.ref ? T.xs + (size_t)nExp * 4 : nullptr;
   T.hsBytes = hs;
   m->useMwg = true;
   // The hand-off block's memory: where the parts spread over the XCDs (not pinned), uncached
@@ -1137,9 +1148,10 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
       return NAN;
     return it;
   }
-  // 5: k_cg2d_block in the reference order (cg2dRefOrder), 4: k_cg2d_mwg, 3: k_cg2d_bxy, 2: k_cg2d_blk2, 1: k_cg2d_block
+  // 6: k_cg2d_mwg in the reference order (cg2dRefOrder past one workgroup), 5: k_cg2d_block in the reference order
+  // (cg2dRefOrder), 4: k_cg2d_mwg, 3: k_cg2d_bxy, 2: k_cg2d_blk2, 1: k_cg2d_block
   if (!strcmp(name, "cg2dKernel"))
-    return m->p.cg2dRefOrder ? 5.0 : m->useMwg ? 4.0 : m->nBlkX > 0 ? 3.0 : (m->nBlk > 0 ? 2.0 : 1.0);
+    return m->p.cg2dRefOrder ? (m->useMwg ? 6.0 : 5.0) : m->useMwg ? 4.0 : m->nBlkX > 0 ? 3.0 : (m->nBlk > 0 ? 2.0 : 1.0);
   if (!strcmp(name, "cg2dParts")) return m->useMwg ? (double)m->mwg.G : 1.0;
   // 1 when the multi-workgroup solve's parts are placed on one XCD (one L2: ~1 us hand-offs)
   if (!strcmp(name, "cg2dPinned")) return m->useMwg ? (double)m->mwg.pinned : 0.0;
@@ -1398,13 +1410,16 @@ int mgcm_init(mgcm_model *m) {
   // blocks; otherwise the multi-workgroup solver (the generic single-workgroup kernel measured
   // 12.7 against 4.2 us/iteration on the cube, round 3)
   m->useMwg = false;
-  // cg2dRefOrder: the generic single-workgroup kernel with the reference's summation order
-  // (parity runs on the reference's own tiling; refused where it does not fit one workgroup)
+  // cg2dRefOrder (parity runs on the reference's own tiling): the reference's summation order in
+  // the generic single-workgroup kernel where the grid fits one workgroup, else in the
+  // multi-workgroup solver (k_cg2d_mwg<.., REF>)
   if (m->p.cg2dRefOrder) {
-    if (m->nPts > cg2d_ref_max_points())
-      return set_err("mgcm_init: cg2dRefOrder needs <= %d interior points (one workgroup), have %d",
-                     cg2d_ref_max_points(), m->nPts);
     if (m->p.useSRCGSolver) return set_err("mgcm_init: cg2dRefOrder with useSRCGSolver not implemented");
+    if (m->nPts > cg2d_ref_max_points()) {
+      m->nBlkX = 0;
+      m->nBlk = 0;
+      if (build_mwg(m)) return -1;
+    }
   } else if ((m->nBlkX == 0 && m->nBlk == 0) ||
              ext("cg2dForceMwg", 0.0) != 0.0) {
     // cg2dForceMwg: the multi-workgroup solver on a grid the single-workgroup kernels would
@@ -1522,7 +1537,7 @@ static bool cg2d_fuses_eta(const mgcm_model *m) {
 }
 
 static hipError_t launch_cg2d(mgcm_model *m, int maxIters, int nIterMin, bool fuseEta = false) {
-  if (m->p.cg2dRefOrder)
+  if (m->p.cg2dRefOrder && !m->useMwg)
     return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
                              m->stream);
   if (m->useMwg) {
@@ -2206,6 +2221,9 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
 int mgcm_set_tile_range(mgcm_model *m, int t0, int nT) {
   if (t0 < 0 || nT < 1 || t0 + nT > m->d.nTiles)
     return set_err("mgcm_set_tile_range: tiles [%d, %d) outside [0, %d)", t0, t0 + nT, m->d.nTiles);
+  if (m->useMwg && m->mwg.ref && nT < m->d.nTiles)
+    return set_err("mgcm_set_tile_range: cg2dRefOrder in the multi-workgroup CG2D needs the whole domain's tiles, not the "
+                   "tile range [%d, %d) of %d", t0, t0 + nT, m->d.nTiles);
   m->d.t0 = t0;
   m->d.nT = nT;
   drop_graphs(m);
@@ -2289,6 +2307,15 @@ int mgcm_tile_copy(mgcm_model *m, const char *name, int t0, int nT, void *buf, i
 
 static int mwg_block_uncached(mgcm_model *m);
 
+// cg2dRefOrder in the multi-workgroup CG2D chains the parts of every tile inside ONE launch of
+// the whole domain: no sub-launch of a tile range, no hand-off block shared between processes
+// or models
+static int mwg_ref_refuse(const mgcm_model *m, const char *who) {
+  if (!m->useMwg || !m->mwg.ref) return 0;
+  return set_err("%s: cg2dRefOrder in the multi-workgroup CG2D runs the whole domain in one launch of one model "
+                 "(no tile ranges, no shared hand-off block)", who);
+}
+
 // Everyone sharing a hand-off block must tag with the same launch epoch: the epoch words
 // (each process's / model's own, T.epoch) restart at 0 wherever a block is shared, and the
 // block itself is zeroed by its owner then, so granules an earlier solve of one sharer left
@@ -2310,6 +2337,7 @@ static int mwg_restart_epoch(mgcm_model *m, bool zeroBlock) {
 int mgcm_cg2d_shared_export(mgcm_model *m, void *handle) {
   if (!m->useMwg || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_shared_export: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
+  if (mwg_ref_refuse(m, "mgcm_cg2d_shared_export")) return -1;
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipStreamSynchronize(m->stream));
   // the importers' launches may run on other GPUs: an uncached block (mwg_block_uncached)
@@ -2323,6 +2351,7 @@ int mgcm_cg2d_shared_export(mgcm_model *m, void *handle) {
 int mgcm_cg2d_shared_import(mgcm_model *m, const void *handle) {
   if (!m->useMwg || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_shared_import: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
+  if (mwg_ref_refuse(m, "mgcm_cg2d_shared_import")) return -1;
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipStreamSynchronize(m->stream));
   if (m->mwgShared) { (void)hipIpcCloseMemHandle(m->mwgShared); m->mwgShared = nullptr; }
@@ -2439,6 +2468,7 @@ int mgcm_step_phase(mgcm_model *m, int phase) {
     case 10:  // the device CG2D over this process's parts (hand-off block shared by IPC)
       if (!m->useMwg || m->mwg.partsPerTile <= 0)
         return set_err("mgcm_step_phase(10): needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
+      if (m->d.nT < m->d.nTiles && mwg_ref_refuse(m, "mgcm_step_phase(10) on a tile subset")) return -1;
       if (m->d.nT < m->d.nTiles && !m->mwg.sys)
         return set_err("mgcm_step_phase(10): a tile subset needs the shared hand-off block (mgcm_cg2d_shared_*)");
       TIMED(K_CG2D, launch_cg2d_mwg(m->d, m->p, m->f, m->mwg, m->p.cg2dMaxIters, m->p.cg2dUseMinResSol - 1, m->d_rec, m->d_ctr + 1, m->stream,
@@ -2582,6 +2612,7 @@ int mgcm_cg2d_tiles(mgcm_model *m, int t0, int nT) {
   if (!m->useMwg || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_tiles: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
   if (t0 < 0 || nT < 1 || t0 + nT > m->d.nTiles) return set_err("mgcm_cg2d_tiles: bad tile range");
+  if (nT < m->d.nTiles && mwg_ref_refuse(m, "mgcm_cg2d_tiles on a tile subset")) return -1;
   if (nT < m->d.nTiles && !m->mwg.sys)
     return set_err("mgcm_cg2d_tiles: a tile subset needs the shared hand-off block (mgcm_cg2d_share)");
   HIPCHK(hipSetDevice(m->device));
@@ -2605,6 +2636,7 @@ static int mwg_block_realloc(mgcm_model *m, int mem, bool sys) {
   m->mwg.ctr = (unsigned *)blk;
   m->mwg.part = (unsigned long long *)(blk + 64);
   m->mwg.xs = m->mwg.part + partGr;
+  m->mwg.refc = m->mwg.ref ? m->mwg.xs + (size_t)m->mwg.nExp * 4 : nullptr;
   m->mwg.sys = sys ? 1 : 0;
   drop_graphs(m);
   return 0;
@@ -2624,6 +2656,7 @@ static int mwg_block_uncached(mgcm_model *m) {
 int mgcm_cg2d_share(mgcm_model *m, mgcm_model *owner) {
   if (!m->useMwg || !owner->useMwg || m->mwg.partsPerTile <= 0 || m->mwg.G != owner->mwg.G)
     return set_err("mgcm_cg2d_share: both models need the same whole-domain multi-workgroup CG2D (cg2dForceMwg)");
+  if (mwg_ref_refuse(m, "mgcm_cg2d_share") || mwg_ref_refuse(owner, "mgcm_cg2d_share")) return -1;
   HIPCHK(hipSetDevice(owner->device));
   HIPCHK(hipStreamSynchronize(owner->stream));
   if (mwg_block_uncached(owner)) return -1;

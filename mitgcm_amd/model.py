@@ -202,10 +202,10 @@ class Model:
 
     def cg2d_kernel(self):
         """Which CG2D kernel mgcm_init selected: 'mwg' (multi-workgroup), 'bxy' (BX x BY points/thread),
-        'blk2' (2x2), 'block', or 'block_ref' (k_cg2d_block summing in the reference's order,
-        cg2dRefOrder)."""
+        'blk2' (2x2), 'block', or, summing in the reference's order (cg2dRefOrder), 'block_ref'
+        (k_cg2d_block, up to one workgroup's points) and 'mwg_ref' (multi-workgroup, past that)."""
         k = lib().mgcm_get_param(self.h, b"cg2dKernel")
-        return {5.0: "block_ref", 4.0: "mwg", 3.0: "bxy", 2.0: "blk2"}.get(k, "block")
+        return {6.0: "mwg_ref", 5.0: "block_ref", 4.0: "mwg", 3.0: "bxy", 2.0: "blk2"}.get(k, "block")
 
     def step_layout(self):
         """The launch layout of the last step built (mgcm_get_param 'stepLayout'): which
