@@ -42,7 +42,7 @@
 // publishes the tile partial, and every part adds the nTiles partials itself (mw_sync_ref).
 // Two hand-offs per iteration as above, the same granules, tags and double buffering; no tree,
 // no DPP in any sum.  The parity mode: a chain costs sNx*sNy dependent adds per sum.
-#include "common.h"
+#include "cg2d.h"
 
 namespace mgcm {
 

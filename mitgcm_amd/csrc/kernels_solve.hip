@@ -7,20 +7,20 @@
 //
 // CG2D is latency-bound at the BASELINE grids (3.6k-6k points, ~100 iterations
 // per solve, 3 global sums + 2 halo exchanges per iteration in the reference):
-// a launch per phase would cost more than the arithmetic.  k_cg2d_block runs
-// the WHOLE solve in ONE workgroup of 1024 threads:
+// a launch per phase would cost more than the arithmetic.  The single-workgroup
+// solvers (k_cg2d_bxy, and k_cg2d_block for the reference's summation order) run
+// the WHOLE solve in ONE workgroup:
 //   * r and s live in LDS (interior points only, compact); the halo exchange
 //     of EXCH_S3D_RL becomes a neighbour-index table (halo point -> the interior
 //     point it is a copy of), so an exchange costs nothing;
-//   * x, s, r and (as register room allows) the 10 operator coefficients of
-//     each point stay in VGPRs;
-//   * each global sum is a DPP row reduction + 4 readlanes per wave, one LDS
-//     slot per wave, one barrier, and a DPP row reduction of the 16 wave
-//     partials; every lane ends with the bit-identical sum (no broadcast,
-//     run-to-run deterministic).
+//   * x, s, r of each point stay in VGPRs, and in k_cg2d_bxy the operator
+//     coefficients of the thread's block too;
+//   * k_cg2d_bxy's global sums are a DPP row reduction per wave, one LDS slot per
+//     wave, one barrier, and a register tree over the wave partials; every lane
+//     ends with the bit-identical sum (no broadcast, run-to-run deterministic).
 #include <cstdlib>
 
-#include "common.h"
+#include "cg2d.h"
 
 namespace mgcm {
 
@@ -39,15 +39,6 @@ __device__ __forceinline__ double dpp_f64(double v) {
   const long long b = __builtin_bit_cast(long long, v);
   const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffff), CTRL, 0xF, 0xF, true);
   const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-// row_bcast15 (rows 1,3 <- lane 15 of rows 0,2) / row_bcast31 (rows 2,3 <- lane 31);
-// rows outside ROWMASK receive +0.0, which leaves their partial unchanged.
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_bcast_f64(double v) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffff), CTRL, ROWMASK, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROWMASK, 0xF, false);
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 __device__ __forceinline__ double row_sum16(double v) {
@@ -70,31 +61,14 @@ __device__ __forceinline__ double lane_f64(double v, int l) {
   const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
-// wave sum, uniform (SGPR) result: rows by DPP, then row1 += row0, row3 += row2
-// (row_bcast15) and rows 2,3 += lane 31 (row_bcast31): lane 63 holds
-// (r3+r2)+(r1+r0), the same value as (r0+r1)+(r2+r3).
-__device__ __forceinline__ double wave_sum(double v) {
-  v = row_sum16(v);
-  v = v + dpp_bcast_f64<0x142, 0xA>(v);
-  v = v + dpp_bcast_f64<0x143, 0xC>(v);
-  return lane_f64(v, 63);
-}
 __device__ __forceinline__ double wave_max(double v) {
   v = row_max16(v);
   return fmax(fmax(lane_f64(v, 0), lane_f64(v, 16)), fmax(lane_f64(v, 32), lane_f64(v, 48)));
 }
 
-// Block-wide sum over the 16 waves; `slot` selects one of 4 rotating LDS
-// partial buffers so consecutive reductions need only one barrier each.  After
-// the barrier lane l of every wave reads partial[l & 15] and reduces its row:
-// every lane of the block ends with the same, bit-identical sum.
-__device__ __forceinline__ double block_sum(double v, double *red, int slot) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) red[slot * CG_WAVES + wv] = v;
-  __syncthreads();
-  return row_sum16(red[slot * CG_WAVES + (lane & 15)]);
-}
+// Block-wide maximum over the 16 waves of k_cg2d_block: one LDS partial per wave at
+// red[slot * CG_WAVES + wave], one barrier; lane l of every wave then reads partial[l & 15]
+// and reduces its row, so every lane of the block ends with the same value.
 __device__ __forceinline__ double block_max(double v, double *red, int slot) {
   v = wave_max(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -106,7 +80,7 @@ __device__ __forceinline__ double block_max(double v, double *red, int slot) {
 // GLOBAL_SUM_TILE_RL in the reference's own order (cg2d.F:211-243 / 305-337 +
 // global_sum_tile.F:161-191): every tile's interior terms added sequentially, j outer and
 // i inner, from 0.0, then the tile partials added in tile order (bi fastest), from 0.0.
-// The per-point terms go through LDS at their compact index (tile, j, i: build_nbr's
+// The per-point terms go through LDS at their compact index (tile, j, i: build_block's
 // order), one thread per tile sums them, and every thread adds the tile partials itself
 // (identical values, no broadcast).  Costs two barriers and a serial chain of sNx*sNy adds
 // per sum: the parity mode, not the performance path (cg2dRefOrder).
@@ -224,35 +198,36 @@ __global__ void __launch_bounds__(256) k_sfp_rhs_march(Dims d, Params p, Fields 
   f.cg2d_b[q] = b;
 }
 
-// Whole-solve CG2D in one workgroup.  PPT = interior points per thread.
+// Whole-solve CG2D in one workgroup, every global sum in the reference's own order (ref_sum):
+// the cg2dRefOrder solver of a grid of up to cg2d_ref_max_points() points.  PPT = interior
+// points per thread.
 // Points are padded to NP = PPT*1024: a padding point has x = b = 0, every
 // neighbour index pointing at the ZERO slot (index NP, never written), so it
 // stays exactly 0 through every phase and the per-point code is branch-free.
 // nbr[2*NP]: packed compact neighbour indices (W | E<<16), (S | N<<16); when the
 // neighbour is a halo point, the index is the interior point the halo is a copy
-// of (EXCH_S3D_RL / EXCH_XY_RL).  CREG: how many of the two 5-coefficient sets
-// (A, then M) stay in VGPRs; the rest is re-read each use from L2.
-template <int PPT, bool MINRES, int CREG, bool REFSUM = false>
+// of (EXCH_S3D_RL / EXCH_XY_RL).  The ten operator coefficients of a point are re-read
+// from L2 at each use.
+template <int PPT, bool MINRES>
 __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fields f, const unsigned *__restrict__ nbr,
                                                           const int *__restrict__ gofs, int nPts, int maxIters,
                                                           int nIterMinIn, SolveRecord *rec, int *stepCounter) {
+  static_assert(PPT == 1 || PPT == 2 || PPT == 4, "k_cg2d_block: PPT");
   constexpr int NP = PPT * CG_THREADS;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double *r_l = lds;                // NP + 1 (last = ZERO slot)
   double *s_l = lds + (NP + 1);     // NP + 1
-  double *red = lds + 2 * (NP + 1); // 4 * CG_WAVES
-  // REFSUM (cg2dRefOrder): per-point terms and tile partials of the reference-order sums
+  double *red = lds + 2 * (NP + 1); // 4 * CG_WAVES (block_max)
+  // per-point terms and tile partials of the reference-order sums
   double *term_l = red + 4 * CG_WAVES;   // NP
   double *tile_l = term_l + NP;          // nTiles
   const int nTilesR = d.nTiles, tilePts = d.sNx * d.sNy;
   const int tid = threadIdx.x;
-  constexpr int RA = (CREG >= 1) ? PPT : 1, RM = (CREG >= 2) ? PPT : 1, RX = MINRES ? PPT : 1;
+  constexpr int RX = MINRES ? PPT : 1;
 
   unsigned g[PPT];  // BYTE offset of the point in a 2-D field (32-bit: saddr-mode loads)
   unsigned nwe[PPT], nsn[PPT];
   double x[PPT], s[PPT], r[PPT], xmin[RX];
-  double aW0r[RA], aW1r[RA], aS0r[RA], aS1r[RA], aCr[RA];
-  double pCr[RM], pW0r[RM], pW1r[RM], pS0r[RM], pS1r[RM];
   const unsigned dE = 8u, dN = 8u * (unsigned)d.nx;
   // buffer descriptors (32-bit voffset + immediate offsets: one VGPR per point
   // addresses all ten coefficient loads; guide T8)
@@ -266,16 +241,13 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
 #define BLD(rs, off) __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, (off), 0, 0))
 #define LDO(base, off) (*(const double *)((const char *)(base) + (off)))
 #define STO(base, off) (*(double *)((char *)(base) + (off)))
-#define aW0(m) ((CREG >= 1) ? aW0r[(CREG >= 1) ? m : 0] : BLD(rsW, g[m]))
-#define aW1(m) ((CREG >= 1) ? aW1r[(CREG >= 1) ? m : 0] : BLD(rsW, g[m] + dE))
-#define aS0(m) ((CREG >= 1) ? aS0r[(CREG >= 1) ? m : 0] : BLD(rsS, g[m]))
-#define aS1(m) ((CREG >= 1) ? aS1r[(CREG >= 1) ? m : 0] : BLD(rsS, g[m] + dN))
-#define aC(m) ((CREG >= 1) ? aCr[(CREG >= 1) ? m : 0] : BLD(rsC, g[m]))
-#define pC(m) ((CREG >= 2) ? pCr[(CREG >= 2) ? m : 0] : BLD(rpC, g[m]))
-#define pW0(m) ((CREG >= 2) ? pW0r[(CREG >= 2) ? m : 0] : BLD(rpW, g[m]))
-#define pW1(m) ((CREG >= 2) ? pW1r[(CREG >= 2) ? m : 0] : BLD(rpW, g[m] + dE))
-#define pS0(m) ((CREG >= 2) ? pS0r[(CREG >= 2) ? m : 0] : BLD(rpS, g[m]))
-#define pS1(m) ((CREG >= 2) ? pS1r[(CREG >= 2) ? m : 0] : BLD(rpS, g[m] + dN))
+// A x = aW0 x(i-1) + aW1 x(i+1) + aS0 x(j-1) + aS1 x(j+1) + aC x ; M r likewise with pW, pS, pC
+#define A_APPLY(m, v_l, v)                                                                                 \
+  (BLD(rsW, g[m]) * v_l[LO(nwe[m])] + BLD(rsW, g[m] + dE) * v_l[HI(nwe[m])] + BLD(rsS, g[m]) * v_l[LO(nsn[m])] + \
+   BLD(rsS, g[m] + dN) * v_l[HI(nsn[m])] + BLD(rsC, g[m]) * v[m])
+#define M_APPLY(m, v_l, v)                                                                                 \
+  (BLD(rpC, g[m]) * v[m] + BLD(rpW, g[m]) * v_l[LO(nwe[m])] + BLD(rpW, g[m] + dE) * v_l[HI(nwe[m])] +           \
+   BLD(rpS, g[m]) * v_l[LO(nsn[m])] + BLD(rpS, g[m] + dN) * v_l[HI(nsn[m])])
 #define LO(w) ((w) & 0xFFFFu)
 #define HI(w) ((w) >> 16)
 #define ACT(m) (tid + (m) * CG_THREADS < nPts)
@@ -288,16 +260,6 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
     g[m] = 8u * (unsigned)gofs[pt];
     nwe[m] = nbr[2 * pt];
     nsn[m] = nbr[2 * pt + 1];
-    if (CREG >= 1) {
-      const int mm = (CREG >= 1) ? m : 0;
-      aW0r[mm] = BLD(rsW, g[m]); aW1r[mm] = BLD(rsW, g[m] + dE); aS0r[mm] = BLD(rsS, g[m]); aS1r[mm] = BLD(rsS, g[m] + dN);
-      aCr[mm] = BLD(rsC, g[m]);
-    }
-    if (CREG >= 2) {
-      const int mm = (CREG >= 2) ? m : 0;
-      pCr[mm] = BLD(rpC, g[m]); pW0r[mm] = BLD(rpW, g[m]); pW1r[mm] = BLD(rpW, g[m] + dE); pS0r[mm] = BLD(rpS, g[m]);
-      pS1r[mm] = BLD(rpS, g[m] + dN);
-    }
     b[m] = ACT(m) ? LDO(f.cg2d_b, g[m]) : 0.0;
     x[m] = ACT(m) ? LDO(f.cg2d_x, g[m]) : 0.0;
     s[m] = 0.0;
@@ -319,27 +281,18 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
   for (int m = 0; m < PPT; m++) s_l[tid + m * CG_THREADS] = x[m];
   __syncthreads();
   // cg2d.F:139-180: r = b - A x ; err_sq, sumRHS
-  double err = 0.0, sumB = 0.0, tq[PPT];
+  double tq[PPT];   // the per-point terms of the sum in hand
 #pragma unroll
   for (int m = 0; m < PPT; m++) {
-    r[m] = b[m] - (aW0(m) * s_l[LO(nwe[m])] + aW1(m) * s_l[HI(nwe[m])] + aS0(m) * s_l[LO(nsn[m])] +
-                   aS1(m) * s_l[HI(nsn[m])] + aC(m) * x[m]);
-    err = err + r[m] * r[m];
-    sumB = sumB + b[m];
+    r[m] = b[m] - A_APPLY(m, s_l, x);
     tq[m] = r[m] * r[m];
     if (MINRES) xmin[MINRES ? m : 0] = x[m];
   }
 #pragma unroll
   for (int m = 0; m < PPT; m++)
     if (ACT(m)) STO(f.cg2d_b, g[m]) = b[m];  // cg2d_b is INOUT (normalised in place)
-  double err_sq, sumRHS;
-  if (REFSUM) {
-    err_sq = ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts);
-    sumRHS = ref_sum<PPT>(b, term_l, tile_l, nTilesR, tilePts);
-  } else {
-    err_sq = block_sum(err, red, 1);
-    sumRHS = block_sum(sumB, red, 2);
-  }
+  double err_sq = ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts);
+  const double sumRHS = ref_sum<PPT>(b, term_l, tile_l, nTilesR, tilePts);
   // EXCH_S3D_RL(cg2d_r): r into LDS; s_l re-zeroed for s = q + beta*s
 #pragma unroll
   for (int m = 0; m < PPT; m++) { r_l[tid + m * CG_THREADS] = r[m]; s_l[tid + m * CG_THREADS] = 0.0; }
@@ -350,23 +303,18 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
   int actualIts = 0;
   double eta_qrNM1 = 1.0;
   __syncthreads();
-  int slot = 3;
   if (!(err_sq < p.cg2dTolerance_sq)) {
     for (int it2d = 1; it2d <= maxIters; it2d++) {
       // keep L2-resident coefficients out of VGPRs: forbid hoisting their loads
-      if (CREG < 2) asm volatile("" ::: "memory");
+      asm volatile("" ::: "memory");
       // q = M r ; eta_qrN = sum q*r   (cg2d.F:211-243)
       double q[PPT];
-      double e = 0.0;
 #pragma unroll
       for (int m = 0; m < PPT; m++) {
-        q[m] = pC(m) * r[m] + pW0(m) * r_l[LO(nwe[m])] + pW1(m) * r_l[HI(nwe[m])] + pS0(m) * r_l[LO(nsn[m])] +
-               pS1(m) * r_l[HI(nsn[m])];
-        e = e + q[m] * r[m];
+        q[m] = M_APPLY(m, r_l, r);
         tq[m] = q[m] * r[m];
       }
-      slot = (slot + 1) & 3;
-      const double eta_qrN = REFSUM ? ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts) : block_sum(e, red, slot);
+      const double eta_qrN = ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts);
       const double cgBeta = eta_qrN / eta_qrNM1;
       eta_qrNM1 = eta_qrN;
       // s = q + beta*s ; EXCH_S3D_RL(cg2d_s)
@@ -374,31 +322,24 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
       for (int m = 0; m < PPT; m++) { s[m] = q[m] + cgBeta * s[m]; s_l[tid + m * CG_THREADS] = s[m]; }
       __syncthreads();
       // q = A s ; alpha = sum s*q   (cg2d.F:268-301)
-      double a = 0.0;
 #pragma unroll
       for (int m = 0; m < PPT; m++) {
-        q[m] = aW0(m) * s_l[LO(nwe[m])] + aW1(m) * s_l[HI(nwe[m])] + aS0(m) * s_l[LO(nsn[m])] +
-               aS1(m) * s_l[HI(nsn[m])] + aC(m) * s[m];
-        a = a + s[m] * q[m];
+        q[m] = A_APPLY(m, s_l, s);
         tq[m] = s[m] * q[m];
       }
-      slot = (slot + 1) & 3;
-      double alpha = REFSUM ? ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts) : block_sum(a, red, slot);
+      double alpha = ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts);
       alpha = eta_qrN / alpha;
       // x += alpha s ; r -= alpha q ; err_sq   (cg2d.F:305-328)
-      double e2 = 0.0;
 #pragma unroll
       for (int m = 0; m < PPT; m++) {
         x[m] = x[m] + alpha * s[m];
         r[m] = r[m] - alpha * q[m];
-        e2 = e2 + r[m] * r[m];
         tq[m] = r[m] * r[m];
         r_l[tid + m * CG_THREADS] = r[m];
       }
       actualIts = it2d;
-      slot = (slot + 1) & 3;
-      // the barrier of either sum also publishes r_l (EXCH_S3D_RL(cg2d_r))
-      err_sq = REFSUM ? ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts) : block_sum(e2, red, slot);
+      // the sum's barriers also publish r_l (EXCH_S3D_RL(cg2d_r))
+      err_sq = ref_sum<PPT>(tq, term_l, tile_l, nTilesR, tilePts);
       if (err_sq < p.cg2dTolerance_sq) break;
       if (MINRES && err_sq < minResidualSq) {
         minResidualSq = err_sq;
@@ -434,272 +375,8 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_block(Dims d, Params p, Fie
 #undef LDO
 #undef BLD
 #undef STO
-#undef aW0
-#undef aW1
-#undef aS0
-#undef aS1
-#undef aC
-#undef pC
-#undef pW0
-#undef pW1
-#undef pS0
-#undef pS1
-}
-
-// 2x2-blocked whole-solve CG2D (<= 4096 points): each thread owns a 2x2 block of
-// mutually adjacent interior points P[b][a] (row b, column a; P[0][1] east of
-// P[0][0], P[1][*] north of P[0][*]).  Blocks are formed on the global lat-lon
-// index space, so a block may straddle a tile edge and odd tile sizes work as
-// long as the global Nx, Ny are even; each point carries its own 2-D offset.
-// The block's four in-block neighbour values come from its own registers; only
-// the eight out-of-block ones (two per side) are LDS reads through the
-// neighbour table, and all 32 operator coefficients of the block (aW/pW of the
-// three W-E faces of each row, aS/pS of the three S-N faces of each column, aC,
-// pC) stay in VGPRs (pS, pC in LDS).  No FMA contraction (built -ffp-contract=off like
-// every kernel): each operator row is the reference's expression tree, so only the
-// order of the global sums differs from cg2d.F.
-// nb4[4*T]: packed 16-bit compact indices (W0|W1<<16), (E0|E1<<16),
-// (S0|S1<<16), (N0|N1<<16); blk[4*T] = 2-D offsets of P00, P10(east), P01(north),
-// P11 (T = #blocks; padding blocks: offsets of a real block, inactive).
-template <bool MINRES>
-__global__ void __launch_bounds__(CG_THREADS) k_cg2d_blk2(Dims d, Params p, Fields f, const unsigned *__restrict__ nb4,
-                                                         const int *__restrict__ blk, int nBlk, int maxIters,
-                                                         int nIterMinIn, SolveRecord *rec, int *stepCounter) {
-  constexpr int NP = 4 * CG_THREADS;
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double *r_l = lds;                // NP + 1 (last = ZERO slot)
-  double *s_l = lds + (NP + 1);
-  double *red = lds + 2 * (NP + 1);
-  const int tid = threadIdx.x;
-  const bool act = tid < nBlk;
-  const int bt = act ? tid : 0;
-  const long nx = d.nx;
-  // G[b][a]: 2-D offset of point P[b][a]; compact LDS slot: tile-major, row-major in the tile
-  const long G[2][2] = {{blk[4 * bt], blk[4 * bt + 1]}, {blk[4 * bt + 2], blk[4 * bt + 3]}};
-  auto slot_of = [&](long gg) {
-    const int tt = (int)(gg / d.n2), ll = (int)(gg % d.n2);
-    return tt * d.sNx * d.sNy + (ll / d.nx - d.OLy) * d.sNx + (ll % d.nx - d.OLx);
-  };
-  const int c00 = act ? slot_of(G[0][0]) : NP, c10 = act ? slot_of(G[0][1]) : NP;
-  const int c01 = act ? slot_of(G[1][0]) : NP, c11 = act ? slot_of(G[1][1]) : NP;
-  const unsigned wW = nb4[4 * bt], wE = nb4[4 * bt + 1], wS = nb4[4 * bt + 2], wN = nb4[4 * bt + 3];
-#define LO(w) ((w) & 0xFFFFu)
-#define HI(w) ((w) >> 16)
-  // coefficients (halo-inclusive arrays: the i0+2 / j0+2 entries may be halo values,
-  // exactly what the reference reads after EXCH_UV_XY_RS / EXCH_XY_RS)
-  const double az = act ? 1.0 : 0.0;
-  // A (aW, aS, aC) and pW stay in VGPRs; pS and pC (10 values) live in LDS,
-  // structure-of-arrays over threads (conflict-free), to stay under 128 VGPRs.
-  double *pl = red + 4 * CG_WAVES;  // 10 * CG_THREADS
-  double aW[2][3], pW[2][3], aS[2][3], aC[2][2];
-  // W-E faces of row b: west faces of P[b][0], P[b][1], and the east face of P[b][1]
-  // (its i+1 entry: the halo copy of the eastern neighbour's coefficient when P[b][1]
-  // is on a tile edge, exactly what the reference reads after EXCH_UV_XY_RS)
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const long gw = a < 2 ? G[b][a] : G[b][1] + 1;
-      const long gs = a < 2 ? G[a][b] : G[1][b] + nx;
-      aW[b][a] = az * f.aW2d[gw];
-      pW[b][a] = az * f.pW[gw];
-      aS[b][a] = az * f.aS2d[gs];  // [column b][row a]
-      pl[(b * 3 + a) * CG_THREADS + tid] = az * f.pS[gs];
-    }
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-      aC[b][a] = az * f.aC2d[G[b][a]];   // [row b][col a]
-      pl[(6 + b * 2 + a) * CG_THREADS + tid] = az * f.pC[G[b][a]];
-    }
-#define pS(b, a) pl[((b) * 3 + (a)) * CG_THREADS + tid]
-#define pC(b, a) pl[(6 + (b) * 2 + (a)) * CG_THREADS + tid]
-  // state of the 4 points, index [row b][col a]
-  double x[2][2], r[2][2], s[2][2], b_[2][2];
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-      b_[b][a] = act ? f.cg2d_b[G[b][a]] : 0.0;
-      x[b][a] = act ? f.cg2d_x[G[b][a]] : 0.0;
-      s[b][a] = 0.0;
-    }
-  if (tid == 0) { r_l[NP] = 0.0; s_l[NP] = 0.0; }
-  const int cs[2][2] = {{c00, c10}, {c01, c11}};
-
-  // 5-point operator on the block: out[b][a] = sum of coef*value (reference order C?:
-  // A: aW*v(i-1)+aW(i+1)*v(i+1)+aS*v(j-1)+aS(j+1)*v(j+1)+aC*v ; M: pC*v+pW*..+pS*..)
-#define NEIGH(arr, v, vW0, vW1, vE0, vE1, vS0, vS1, vN0, vN1)                                              \
-  const double vW0 = arr[LO(wW)], vW1 = arr[HI(wW)], vE0 = arr[LO(wE)], vE1 = arr[HI(wE)];                \
-  const double vS0 = arr[LO(wS)], vS1 = arr[HI(wS)], vN0 = arr[LO(wN)], vN1 = arr[HI(wN)];
-#define APPLY_A(out, v, vW0, vW1, vE0, vE1, vS0, vS1, vN0, vN1)                                            \
-  out[0][0] = aW[0][0] * vW0 + aW[0][1] * v[0][1] + aS[0][0] * vS0 + aS[0][1] * v[1][0] + aC[0][0] * v[0][0]; \
-  out[0][1] = aW[0][1] * v[0][0] + aW[0][2] * vE0 + aS[1][0] * vS1 + aS[1][1] * v[1][1] + aC[0][1] * v[0][1]; \
-  out[1][0] = aW[1][0] * vW1 + aW[1][1] * v[1][1] + aS[0][1] * v[0][0] + aS[0][2] * vN0 + aC[1][0] * v[1][0]; \
-  out[1][1] = aW[1][1] * v[1][0] + aW[1][2] * vE1 + aS[1][1] * v[0][1] + aS[1][2] * vN1 + aC[1][1] * v[1][1];
-#define APPLY_M(out, v, vW0, vW1, vE0, vE1, vS0, vS1, vN0, vN1)                                            \
-  out[0][0] = pC(0, 0) * v[0][0] + pW[0][0] * vW0 + pW[0][1] * v[0][1] + pS(0, 0) * vS0 + pS(0, 1) * v[1][0]; \
-  out[0][1] = pC(0, 1) * v[0][1] + pW[0][1] * v[0][0] + pW[0][2] * vE0 + pS(1, 0) * vS1 + pS(1, 1) * v[1][1]; \
-  out[1][0] = pC(1, 0) * v[1][0] + pW[1][0] * vW1 + pW[1][1] * v[1][1] + pS(0, 1) * v[0][0] + pS(0, 2) * vN0; \
-  out[1][1] = pC(1, 1) * v[1][1] + pW[1][1] * v[1][0] + pW[1][2] * vE1 + pS(1, 1) * v[0][1] + pS(1, 2) * vN1;
-
-  // cg2d.F:104-133: normalise the RHS
-  double rhsMax = 0.0;
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 2; a++) { b_[b][a] = b_[b][a] * p.cg2dNorm; rhsMax = fmax(fabs(b_[b][a]), rhsMax); }
-  rhsMax = block_max(rhsMax, red, 0);
-  double rhsNorm = 1.0;
-  if (p.cg2dNormaliseRHS) {
-    if (rhsMax != 0.0) rhsNorm = 1.0 / rhsMax;
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) { b_[b][a] = b_[b][a] * rhsNorm; x[b][a] = x[b][a] * rhsNorm; }
-  }
-  // EXCH_XY_RL(cg2d_x) through LDS
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 2; a++) s_l[cs[b][a]] = x[b][a];
-  if (tid == 0) s_l[NP] = 0.0;
-  __syncthreads();
-  double err = 0.0, sumB = 0.0;
-  {
-    double ax[2][2];
-    NEIGH(s_l, x, xW0, xW1, xE0, xE1, xS0, xS1, xN0, xN1)
-    APPLY_A(ax, x, xW0, xW1, xE0, xE1, xS0, xS1, xN0, xN1)
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) {
-        r[b][a] = b_[b][a] - ax[b][a];
-        err = err + r[b][a] * r[b][a];
-        sumB = sumB + b_[b][a];
-      }
-  }
-  double xmin[2][2];
-  if (MINRES) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) xmin[b][a] = x[b][a];
-  }
-  if (act) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) f.cg2d_b[G[b][a]] = b_[b][a];
-  }
-  double err_sq = block_sum(err, red, 1);
-  const double sumRHS = block_sum(sumB, red, 2);
-#pragma unroll
-  for (int b = 0; b < 2; b++)
-#pragma unroll
-    for (int a = 0; a < 2; a++) { r_l[cs[b][a]] = r[b][a]; s_l[cs[b][a]] = 0.0; }
-  if (tid == 0) { r_l[NP] = 0.0; s_l[NP] = 0.0; }
-  const double firstResidual = sqrt(err_sq);
-  int nIterMin = nIterMinIn;
-  double minResidualSq = -1.0;
-  if (MINRES && nIterMin >= 0) { nIterMin = 0; minResidualSq = err_sq; }
-  int actualIts = 0;
-  double eta_qrNM1 = 1.0;
-  __syncthreads();
-  int slot = 3;
-  if (!(err_sq < p.cg2dTolerance_sq)) {
-    for (int it2d = 1; it2d <= maxIters; it2d++) {
-      asm volatile("" ::: "memory");  // re-read pS/pC from LDS every iteration (no hoisting into VGPRs)
-      double q[2][2];
-      double e = 0.0;
-      {
-        NEIGH(r_l, r, rW0, rW1, rE0, rE1, rS0, rS1, rN0, rN1)
-        APPLY_M(q, r, rW0, rW1, rE0, rE1, rS0, rS1, rN0, rN1)
-      }
-#pragma unroll
-      for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int a = 0; a < 2; a++) e = e + q[b][a] * r[b][a];
-      slot = (slot + 1) & 3;
-      const double eta_qrN = block_sum(e, red, slot);
-      const double cgBeta = eta_qrN / eta_qrNM1;
-      eta_qrNM1 = eta_qrN;
-#pragma unroll
-      for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int a = 0; a < 2; a++) { s[b][a] = q[b][a] + cgBeta * s[b][a]; s_l[cs[b][a]] = s[b][a]; }
-      __syncthreads();
-      double aa = 0.0;
-      {
-        NEIGH(s_l, s, sW0, sW1, sE0, sE1, sS0, sS1, sN0, sN1)
-        APPLY_A(q, s, sW0, sW1, sE0, sE1, sS0, sS1, sN0, sN1)
-      }
-#pragma unroll
-      for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int a = 0; a < 2; a++) aa = aa + s[b][a] * q[b][a];
-      slot = (slot + 1) & 3;
-      double alpha = block_sum(aa, red, slot);
-      alpha = eta_qrN / alpha;
-      double e2 = 0.0;
-#pragma unroll
-      for (int b = 0; b < 2; b++)
-#pragma unroll
-        for (int a = 0; a < 2; a++) {
-          x[b][a] = x[b][a] + alpha * s[b][a];
-          r[b][a] = r[b][a] - alpha * q[b][a];
-          e2 = e2 + r[b][a] * r[b][a];
-          r_l[cs[b][a]] = r[b][a];
-        }
-      actualIts = it2d;
-      slot = (slot + 1) & 3;
-      err_sq = block_sum(e2, red, slot);
-      if (err_sq < p.cg2dTolerance_sq) break;
-      if (MINRES && err_sq < minResidualSq) {
-        minResidualSq = err_sq;
-        nIterMin = it2d;
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-          for (int a = 0; a < 2; a++) xmin[b][a] = x[b][a];
-      }
-    }
-  }
-  if (MINRES && nIterMin >= 0 && err_sq > minResidualSq) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) x[b][a] = xmin[b][a];
-  }
-  if (act) {
-#pragma unroll
-    for (int b = 0; b < 2; b++)
-#pragma unroll
-      for (int a = 0; a < 2; a++) {
-        double xv = x[b][a];
-        if (p.cg2dNormaliseRHS) xv = xv / rhsNorm;
-        f.cg2d_x[G[b][a]] = xv;
-      }
-  }
-  if (tid == 0) {
-    const int st = stepCounter ? *stepCounter : 0;
-    SolveRecord &R = rec[st];
-    R.firstResidual = firstResidual;
-    R.lastResidual = sqrt(err_sq);
-    R.minResidualSq = minResidualSq;
-    R.rhsMax = rhsMax;
-    R.sumRHS = sumRHS;
-    R.numIters = actualIts;
-    R.nIterMin = nIterMin;
-  }
-#undef LO
-#undef HI
-#undef NEIGH
-#undef APPLY_A
-#undef APPLY_M
-#undef pS
-#undef pC
+#undef A_APPLY
+#undef M_APPLY
 }
 
 // ---------------------------------------------------------------------------
@@ -710,7 +387,8 @@ __global__ void __launch_bounds__(CG_THREADS) k_cg2d_blk2(Dims d, Params p, Fiel
 // operator coefficient of the block (aW/pW of the BX+1 W-E faces of each row,
 // aS/pS of the BY+1 S-N faces of each column, aC, pC) stays in VGPRs
 // (NT = 512: 2 waves per SIMD, 256 VGPRs each).  Blocks are formed on the global
-// lat-lon index space as for k_cg2d_blk2; r and s live in LDS point-major
+// lat-lon index space, so a block may straddle a tile edge and odd tile sizes work as long
+// as the global Nx, Ny are multiples of BX, BY; r and s live in LDS point-major
 // (slot = p*NT + block, p = b*BX + a), conflict-free for the thread-contiguous
 // gathers and scatters.  nbx[NB/2 per block] packs the
 // 2(BX+BY) out-of-block neighbour slots as 16-bit pairs in the order
@@ -865,7 +543,7 @@ __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, con
 #pragma unroll
     for (int a = 0; a < BX; a++) {
       G[b][a] = blkx[NPT * bt + BX * b + a];
-      // point-major LDS slots (see build_nbr); an idle thread (tid >= nBlk, all its values 0)
+      // point-major LDS slots (see model.hip build_bxy); an idle thread (tid >= nBlk, all its values 0)
       // keeps its own slots, which no block's neighbour table names
       cs[b][a] = (BX * b + a) * NT + tid;
     }
@@ -900,7 +578,7 @@ __global__ void __launch_bounds__(NT) k_cg2d_bxy(Dims d, Params p, Fields f, con
       aC[b][a] = az * f.aC2d[G[b][a]];
       pC[b][a] = az * f.pC[G[b][a]];
     }
-  // The points of the all-land blocks left out of the tables (model.hip build_nbr, dropG): the
+  // The points of the all-land blocks left out of the tables (model.hip build_bxy, dropG): the
   // solve is exact only while b and the first guess are 0.0 on them, so they are scanned here,
   // beside the coefficient loads; a non-zero (or NaN) marks the solve as failed (numIters = -1)
   bool dropBad = false;
@@ -1656,28 +1334,26 @@ hipError_t launch_sfp_rhs(const Dims &d, const Params &p, const Fields &f, hipSt
   return hipGetLastError();
 }
 
+// k_cg2d_block (cg2dRefOrder): r, s and the per-point terms of a sum take 3 NP + nTiles doubles
+// of LDS, which bounds PPT at 4; a grid with more points takes the multi-workgroup solver's
+// reference-order form (k_cg2d_mwg<.., REF>, kernels_cg2d_mwg.hip), so cg2d_ref_max_points()
+// is the threshold between the two
+int cg2d_ref_max_points() { return 4 * CG_THREADS; }
 int cg2d_block_ppt(int nPts) {
-  for (int ppt = 1; ppt <= 8; ppt *= 2)
+  for (int ppt = 1; ppt <= 4; ppt *= 2)
     if (nPts <= ppt * CG_THREADS) return ppt;
   return 0;
 }
-size_t cg2d_block_lds_bytes(int ppt) { return (size_t)(2 * (ppt * CG_THREADS + 1) + 4 * CG_WAVES) * sizeof(double); }
-int cg2d_block_max_points() { return 8 * CG_THREADS; }  // LDS: 2*8193*8 B = 128 KiB
-
-// cg2dRefOrder: the reference-order sums need NP + nTiles more doubles of LDS (PPT <= 4); a
-// grid with more points takes the multi-workgroup solver's reference-order form
-// (k_cg2d_mwg<.., REF>, kernels_cg2d_mwg.hip), so this is the threshold between the two
-int cg2d_ref_max_points() { return 4 * CG_THREADS; }
-static hipError_t launch_cg2d_ref(const Dims &d, const Params &p, const Fields &f, const unsigned *nbr, const int *gofs,
-                                  int nPts, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter,
-                                  hipStream_t s) {
+hipError_t launch_cg2d_block(const Dims &d, const Params &p, const Fields &f, const unsigned *nbr, const int *gofs,
+                             int nPts, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, hipStream_t s) {
   const int ppt = cg2d_block_ppt(nPts);
-  if (!ppt || ppt > 4 || d.nTiles > nPts) return hipErrorInvalidValue;
-  const size_t lds = cg2d_block_lds_bytes(ppt) + (size_t)(ppt * CG_THREADS + d.nTiles) * sizeof(double);
+  if (!ppt || d.nTiles > nPts) return hipErrorInvalidValue;
+  // r_l, s_l (NP + 1 each), block_max's partials, term_l (NP), tile_l (nTiles)
+  const size_t lds = (size_t)(2 * (ppt * CG_THREADS + 1) + 4 * CG_WAVES + ppt * CG_THREADS + d.nTiles) * sizeof(double);
   const bool mr = nIterMin >= 0;
 #define LAUNCH(PPT)                                                                                          \
   do {                                                                                                       \
-    auto kern = mr ? k_cg2d_block<PPT, true, 0, true> : k_cg2d_block<PPT, false, 0, true>;                   \
+    auto kern = mr ? k_cg2d_block<PPT, true> : k_cg2d_block<PPT, false>;                                     \
     hipError_t e_ = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     if (e_ != hipSuccess) return e_;                                                                         \
     hipLaunchKernelGGL(kern, dim3(1), dim3(CG_THREADS), lds, s, d, p, f, nbr, gofs, nPts, maxIters, nIterMin, rec, \
@@ -1692,35 +1368,8 @@ static hipError_t launch_cg2d_ref(const Dims &d, const Params &p, const Fields &
   return hipGetLastError();
 }
 
-hipError_t launch_cg2d_block(const Dims &d, const Params &p, const Fields &f, const unsigned *nbr, const int *gofs,
-                             int nPts, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, hipStream_t s) {
-  if (p.cg2dRefOrder)
-    return launch_cg2d_ref(d, p, f, nbr, gofs, nPts, maxIters, nIterMin, rec, stepCounter, s);
-  const int ppt = cg2d_block_ppt(nPts);
-  if (!ppt) return hipErrorInvalidValue;
-  const size_t lds = cg2d_block_lds_bytes(ppt);
-  const bool mr = nIterMin >= 0;
-#define LAUNCH(PPT)                                                                                        \
-  do {                                                                                                     \
-    constexpr int CR = (PPT <= 2) ? 2 : (PPT <= 4 ? 1 : 0);                                                                 \
-    auto kern = mr ? k_cg2d_block<PPT, true, CR> : k_cg2d_block<PPT, false, CR>;                           \
-    hipError_t e_ = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e_ != hipSuccess) return e_;                                                                       \
-    hipLaunchKernelGGL(kern, dim3(1), dim3(CG_THREADS), lds, s, d, p, f, nbr, gofs, nPts, maxIters, nIterMin, rec, \
-                       stepCounter);                                                                       \
-  } while (0)
-  switch (ppt) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    default: LAUNCH(8); break;
-  }
-#undef LAUNCH
-  return hipGetLastError();
-}
-
 // k_cg2d_bxy geometries (BX x BY points per thread, NT threads): variant v is chosen per
-// grid at set-up (model.hip build_nbr: the global lat-lon index space must tile into
+// grid at set-up (model.hip choose_bxy: the global lat-lon index space must tile into
 // BX x BY blocks, at most NT of them).  Fewer, fatter threads trade serial work per thread
 // for cheaper reductions and barriers (fewer waves).
 struct CgxGeom { int bx, by, nt; };
@@ -1729,7 +1378,7 @@ struct CgxGeom { int bx, by, nt; };
 // (profiles/r02/ocean90/cg2d_geometry.txt).  Under __launch_bounds__(256) 3x4 has the
 // 512-register budget, keeps its overflow in AGPRs and has no scratch; 3x2 x 512 needs 212
 // VGPRs.  Both exceed their thread count on that grid's 3600 points and fit it only with
-// the all-land blocks left out (model.hip build_nbr); there 3x2 x 512 runs 1.40 and
+// the all-land blocks left out (model.hip choose_bxy); there 3x2 x 512 runs 1.40 and
 // 3x4 x 256 1.56 against 2x4 x 512's 1.62 us/iteration (profiles/r07/cg2d_compact/).
 // 3x2 x 512 leads the preference list; 3x4 x 256 fits no grid that 3x2 x 512 does not and is
 // reached through MGCM_CG2D_BXY only.  2x4 x 384 on the compacted grid gained 5.8 % of the
@@ -1781,22 +1430,6 @@ hipError_t launch_cg2d_bxy(int v, const Dims &d, const Params &p, const Fields &
   }
 #undef CGX_CASE
   return hipErrorInvalidValue;
-}
-
-hipError_t launch_cg2d_blk2(const Dims &d, const Params &p, const Fields &f, const unsigned *nb4, const int *blk,
-                            int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, hipStream_t s) {
-  if (nBlk > CG_THREADS) return hipErrorInvalidValue;
-  const size_t lds = cg2d_block_lds_bytes(4) + 10 * CG_THREADS * sizeof(double);  // 146 KiB
-  auto kern = nIterMin >= 0 ? k_cg2d_blk2<true> : k_cg2d_blk2<false>;
-  static bool attrSet[2] = {false, false};   // once per instantiation (not a stream op; keeps graph capture clean)
-  if (!attrSet[nIterMin >= 0]) {
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attrSet[nIterMin >= 0] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(1), dim3(CG_THREADS), lds, s, d, p, f, nb4, blk, nBlk, maxIters, nIterMin, rec,
-                     stepCounter);
-  return hipGetLastError();
 }
 
 hipError_t launch_exchange(const Dims &d, double *a, const long *map, int nHalo, int nz, hipStream_t s) {

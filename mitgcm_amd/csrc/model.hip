@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "../../include/mitgcm_amd.h"
-#include "common.h"
+#include "cg2d.h"
 
 namespace mgcm {
 // Host ranges the Fortran mirror registered for DMA (fortran_abi.hip register_host: the
@@ -59,17 +59,6 @@ hipError_t launch_phi_hyd(const Dims &, const Params &, const Fields &, hipStrea
 bool phys_phi_fusable(const Dims &, const Params &);
 hipError_t launch_phys_phi(const Dims &, const Params &, const Fields &, const int *, hipStream_t);
 hipError_t launch_sfp_rhs(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_cg2d_block(const Dims &, const Params &, const Fields &, const unsigned *, const int *, int, int, int,
-                             SolveRecord *, int *, hipStream_t);
-int cg2d_block_ppt(int nPts);
-int cg2d_ref_max_points();
-hipError_t launch_cg2d_bxy(int, const Dims &, const Params &, const Fields &, const unsigned *, const int *, int, int,
-                           int, SolveRecord *, int *, const int *, const long *, const int *, int, int *, hipStream_t);
-int cg2d_bxy_geometry(int, int *, int *, int *);
-int cg2d_bxy_variants();
-hipError_t launch_cg2d_blk2(const Dims &, const Params &, const Fields &, const unsigned *, const int *, int, int, int,
-                            SolveRecord *, int *, hipStream_t);
-int cg2d_block_max_points();
 hipError_t launch_exchange(const Dims &, double *, const long *, int, int, hipStream_t);
 hipError_t launch_cgd(const Dims &, const Params &, const Fields &, int, double, double *, hipStream_t);
 hipError_t launch_cgd_record(SolveRecord *, const int *, double, double, double, double, int, double, int, hipStream_t);
@@ -111,9 +100,6 @@ bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const Tra
 hipError_t launch_tracer_hpair(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &,
                                const int *, hipStream_t);
 hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, hipStream_t);
-int cg2d_mwg_geometry(int *, int *, int *);
-hipError_t launch_cg2d_mwg(const Dims &, const Params &, const Fields &, const MwgTables &, int, int, SolveRecord *, int *,
-                           hipStream_t, int g0 = 0, int gN = -1);
 }  // namespace mgcm
 
 using namespace mgcm;
@@ -219,21 +205,28 @@ struct mgcm_model {
   long *d_haloAll = nullptr;  // the map of EVERY tile's halo when this model steps a tile subset
   int nHaloAll = 0;           // (EXCH_*_RL on host arrays, mgcm_exchange_host, covers the domain)
   std::vector<long> h_halo;
+  // The CG2D solver, selected once by mgcm_init and never changed after it; every table set
+  // below exists only for the solver that reads it.  The values are those of
+  // mgcm_get_param("cg2dKernel"): 3 k_cg2d_bxy, 4 k_cg2d_mwg, 5 k_cg2d_block (reference order,
+  // cg2dRefOrder on up to one workgroup's points), 6 k_cg2d_mwg in the reference order
+  // (cg2dRefOrder past that).  1 (a generic point-per-thread kernel summing in the tree order)
+  // and 2 (a 2x2-blocked kernel) are retired: no grid could select either any more.
+  enum class Cg2dSolver { Bxy = 3, Mwg = 4, BlockRef = 5, MwgRef = 6 };
+  Cg2dSolver solver = Cg2dSolver::Bxy;
+  bool useMwg() const { return solver == Cg2dSolver::Mwg || solver == Cg2dSolver::MwgRef; }
+  int nPts = 0;               // interior points of the whole domain
+  // BlockRef tables (build_block)
   unsigned *d_nbr = nullptr;  // packed (W|E<<16),(S|N<<16) compact neighbour indices, padded
   int *d_gofs = nullptr;      // 2-D flat offset of each (padded) interior point
-  int nPts = 0;
-  // 2x2-blocked solver tables (even sNx, sNy; <= 1024 blocks)
-  unsigned *d_nb4 = nullptr;
-  int *d_blk = nullptr;
-  int nBlk = 0;
-  // BX x BY-blocked solver tables (k_cg2d_bxy; preferred when the global grid tiles into them)
+  // Bxy tables (build_bxy)
   unsigned *d_nbx = nullptr;
   int *d_blkx = nullptr;
   int nBlkX = 0;
   int bxyVar = -1;              // k_cg2d_bxy geometry (kernels_solve.hip CGX[])
   int *d_slot2 = nullptr;       // per 2-D point: k_cg2d_bxy's LDS slot of its value after EXCH, or -1
-  // land-block compaction of the k_cg2d_bxy tables (build_nbr): the 2-D offsets of the points
-  // of the all-land blocks left out, which the solver's prologue scans for a non-zero
+  // land-block compaction of the k_cg2d_bxy tables (choose_bxy): the 2-D offsets of the points
+  // of the all-land blocks left out, which the solver's prologue scans for a non-zero; empty
+  // under every other solver, so the land guards do nothing there
   std::vector<int> h_dropG;
   int *d_dropG = nullptr;
   int nDropBlk = 0;             // blocks left out (0: the tables cover the whole grid)
@@ -241,8 +234,7 @@ struct mgcm_model {
   int *h_guard = nullptr;       // pinned host word the solver sets when its scan finds a non-zero
   int *d_guard = nullptr;       // its device address
   bool latlonTopology = true;   // false once a custom halo map (e.g. EXCH2 cube) is installed
-  // multi-workgroup CG2D (kernels_cg2d_mwg.hip): tables of every part, device buffers
-  bool useMwg = false;
+  // Mwg, MwgRef tables (build_mwg, kernels_cg2d_mwg.hip): tables of every part, device buffers
   MwgTables mwg{};
   std::vector<void *> mwgAllocs;
   void *mwgShared = nullptr;   // another process's hand-off block, opened by IPC (mgcm_cg2d_shared_import)
@@ -302,6 +294,7 @@ struct mgcm_model {
   double kms[K_N] = {0};
   int kcnt[K_N] = {0};
 };
+using Cg2dSolver = mgcm_model::Cg2dSolver;
 
 static void drop_graphs(mgcm_model *m);
 static int land_eta_check(mgcm_model *m, const char *name, const double *host, long n);
@@ -435,304 +428,275 @@ static int upload_halo(mgcm_model *m) {
   return 0;
 }
 
-// CG2D neighbour table: compact interior index of the value found at the W,E,S,N
-// neighbour (through the halo map when the neighbour is a halo point), packed as
-// two 16-bit indices per word; points are padded to PPT*1024 and padding /
-// missing neighbours point at the ZERO slot (index NP).
-static int build_nbr(mgcm_model *m) {
-  const Dims &d = m->d;
-  const long N2 = d.n2 * d.nTiles;
-  std::vector<long> srcOf(N2, -1);
+// ------------------------------------------------------------------ CG2D tables
+// Each solver reads its own tables, and mgcm_init builds only those of the solver it selected:
+// build_block (BlockRef), build_bxy (Bxy), build_mwg (Mwg, MwgRef).
+template <typename T>
+static int table_upload(T *&dptr, const std::vector<T> &h) {
+  if (dptr) (void)hipFree(dptr);
+  dptr = nullptr;
+  HIPCHK(hipMalloc(&dptr, h.size() * sizeof(T)));
+  HIPCHK(hipMemcpy(dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+// per 2-D point: the interior source of a halo point, -1 otherwise
+static std::vector<long> halo_sources(const mgcm_model *m) {
+  std::vector<long> srcOf((size_t)(m->d.n2 * m->d.nTiles), -1);
   for (size_t h = 0; h + 1 < m->h_halo.size(); h += 2) srcOf[m->h_halo[h]] = m->h_halo[h + 1];
-  m->nPts = d.nTiles * d.sNx * d.sNy;
-  const int ppt = cg2d_block_ppt(m->nPts);
-  if (!ppt) return 0;  // too large for the single-workgroup solver (checked by mgcm_init)
-  const int NP = ppt * 1024;
+  return srcOf;
+}
+// global lat-lon (I, J), 1-based -> tile-local point (i, j, t)
+static void tile_point(const Dims &d, int I, int J, int &i, int &j, int &t) {
+  const int bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
+  t = bj * d.nSx + bi; i = (I - 1) % d.sNx + 1; j = (J - 1) % d.sNy + 1;
+}
+// Compact interior index (tile, j, i) of the point whose value a stencil finds at (i, j, t): the
+// point itself, through the halo map the interior point a halo point is a copy of
+// (EXCH_S3D_RL / EXCH_XY_RL), -1 where there is none.
+static long value_point(const Dims &d, const std::vector<long> &srcOf, int i, int j, int t) {
+  long g = MG_I2(d, i, j, t);
+  if (i < 1 || i > d.sNx || j < 1 || j > d.sNy) g = srcOf[g];
+  if (g < 0) return -1;
+  const long tt = g / d.n2, l = g % d.n2;
+  const int ii = (int)(l % d.nx) - d.OLx + 1, jj = (int)(l / d.nx) - d.OLy + 1;
+  if (ii < 1 || ii > d.sNx || jj < 1 || jj > d.sNy) return -1;
+  return tt * d.sNx * d.sNy + (long)(jj - 1) * d.sNx + (ii - 1);
+}
+
+// k_cg2d_block's tables: per interior point, in compact order, the compact indices of its W, E,
+// S, N values packed as two 16-bit indices per word, and its 2-D offset; points are padded to
+// NP = PPT*1024, and padding / missing neighbours point at the ZERO slot (index NP).
+static int build_block(mgcm_model *m) {
+  const Dims &d = m->d;
+  const int NP = cg2d_block_ppt(m->nPts) * 1024;
+  if (!NP) return set_err("build_block: %d points exceed k_cg2d_block's %d", m->nPts, cg2d_ref_max_points());
+  const std::vector<long> srcOf = halo_sources(m);
   const unsigned ZERO = (unsigned)NP;
-  auto compact = [&](long g) -> unsigned {
-    if (g < 0) return ZERO;
-    long t = g / d.n2, l = g % d.n2;
-    int i = (int)(l % d.nx) - d.OLx + 1, j = (int)(l / d.nx) - d.OLy + 1;
-    if (i < 1 || i > d.sNx || j < 1 || j > d.sNy) return ZERO;
-    return (unsigned)(t * d.sNx * d.sNy + (long)(j - 1) * d.sNx + (i - 1));
+  auto slot = [&](int i, int j, int t) -> unsigned {
+    const long c = value_point(d, srcOf, i, j, t);
+    return c < 0 ? ZERO : (unsigned)c;
   };
   std::vector<unsigned> nb(2 * (size_t)NP, ZERO | (ZERO << 16));
   std::vector<int> gofs(NP, (int)MG_I2(d, 1, 1, 0));
   for (int t = 0; t < d.nTiles; t++)
     for (int j = 1; j <= d.sNy; j++)
       for (int i = 1; i <= d.sNx; i++) {
-        const int pidx = t * d.sNx * d.sNy + (j - 1) * d.sNx + (i - 1);
-        const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
-        unsigned c4[4];
-        for (int c = 0; c < 4; c++) {
-          const int ii = i + di[c], jj = j + dj[c];
-          long g = MG_I2(d, ii, jj, t);
-          if (ii < 1 || ii > d.sNx || jj < 1 || jj > d.sNy) g = srcOf[g];
-          c4[c] = compact(g);
-        }
-        nb[2 * (size_t)pidx] = c4[0] | (c4[1] << 16);
-        nb[2 * (size_t)pidx + 1] = c4[2] | (c4[3] << 16);
+        const size_t pidx = (size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1);
+        nb[2 * pidx] = slot(i - 1, j, t) | (slot(i + 1, j, t) << 16);
+        nb[2 * pidx + 1] = slot(i, j - 1, t) | (slot(i, j + 1, t) << 16);
         gofs[pidx] = (int)MG_I2(d, i, j, t);
       }
-  if (m->d_nbr) (void)hipFree(m->d_nbr);
-  if (m->d_gofs) (void)hipFree(m->d_gofs);
-  HIPCHK(hipMalloc(&m->d_nbr, nb.size() * sizeof(unsigned)));
-  HIPCHK(hipMemcpy(m->d_nbr, nb.data(), nb.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&m->d_gofs, gofs.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(m->d_gofs, gofs.data(), gofs.size() * sizeof(int), hipMemcpyHostToDevice));
-  // 2x2 blocks (k_cg2d_blk2), formed on the global lat-lon index space so that odd
-  // tile sizes work: needs the default EXCH1 lat-lon topology, even global Nx and Ny,
-  // and <= 1024 blocks; the ZERO slot is 4*1024.
-  m->nBlk = 0;
-  const int Nx = d.sNx * d.nSx, Ny = d.sNy * d.nSy;
-  const int nBk = (Nx / 2) * (Ny / 2);
-  if (m->latlonTopology && Nx % 2 == 0 && Ny % 2 == 0 && nBk <= 1024 && !getenv("MGCM_CG2D_NOBLOCKED")) {
-    const unsigned Z = 4096u;
-    auto cmp = [&](long g) -> unsigned {
-      unsigned c = compact(g);
-      return c == ZERO ? Z : c;
-    };
-    auto nbv = [&](int i, int j, int t) -> unsigned {  // value slot of the point (i,j,t), via halo map
-      long g = MG_I2(d, i, j, t);
-      if (i < 1 || i > d.sNx || j < 1 || j > d.sNy) g = srcOf[g];
-      return cmp(g);
-    };
-    // global (I, J), 1-based -> tile-local point
-    auto gpt = [&](int I, int J, int &i, int &j, int &t) {
-      const int bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
-      t = bj * d.nSx + bi; i = (I - 1) % d.sNx + 1; j = (J - 1) % d.sNy + 1;
-    };
-    std::vector<unsigned> nb4(4 * 1024, Z | (Z << 16));
-    std::vector<int> blk(4 * 1024, (int)MG_I2(d, 1, 1, 0));
-    int q = 0;
-    for (int J0 = 1; J0 <= Ny; J0 += 2)
-      for (int I0 = 1; I0 <= Nx; I0 += 2, q++) {
-        int ii[2][2], jj[2][2], tt[2][2];
-        for (int b = 0; b < 2; b++)
-          for (int a = 0; a < 2; a++) gpt(I0 + a, J0 + b, ii[b][a], jj[b][a], tt[b][a]);
-        for (int b = 0; b < 2; b++)
-          for (int a = 0; a < 2; a++) blk[4 * q + 2 * b + a] = (int)MG_I2(d, ii[b][a], jj[b][a], tt[b][a]);
-        // out-of-block neighbours, through each boundary point's own halo map
-        nb4[4 * q + 0] = nbv(ii[0][0] - 1, jj[0][0], tt[0][0]) | (nbv(ii[1][0] - 1, jj[1][0], tt[1][0]) << 16);
-        nb4[4 * q + 1] = nbv(ii[0][1] + 1, jj[0][1], tt[0][1]) | (nbv(ii[1][1] + 1, jj[1][1], tt[1][1]) << 16);
-        nb4[4 * q + 2] = nbv(ii[0][0], jj[0][0] - 1, tt[0][0]) | (nbv(ii[0][1], jj[0][1] - 1, tt[0][1]) << 16);
-        nb4[4 * q + 3] = nbv(ii[1][0], jj[1][0] + 1, tt[1][0]) | (nbv(ii[1][1], jj[1][1] + 1, tt[1][1]) << 16);
-      }
-    if (m->d_nb4) (void)hipFree(m->d_nb4);
-    if (m->d_blk) (void)hipFree(m->d_blk);
-    HIPCHK(hipMalloc(&m->d_nb4, nb4.size() * sizeof(unsigned)));
-    HIPCHK(hipMemcpy(m->d_nb4, nb4.data(), nb4.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&m->d_blk, blk.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(m->d_blk, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->nBlk = nBk;
+  return table_upload(m->d_nbr, nb) || table_upload(m->d_gofs, gofs) ? -1 : 0;
+}
+
+// k_cg2d_bxy's tables (choose_bxy, build_bxy): BX x BY blocks formed on the global lat-lon
+// index space, so they need the default EXCH1 lat-lon topology.
+//
+// Land-block compaction.  A block is left out of the tables when every point of it is a dry
+// column with all four faces closed at every level -- decided from the static arrays
+// INI_CG2D / UPDATE_CG2D build aW2d / aS2d from (h0FacW / h0FacS under the non-linear free
+// surface, else hFacW / hFacS) and from hFacC.  Only the kept blocks are numbered; a left-out
+// point's slot is the ZERO slot, so its neighbours read 0.0, and its slot2 is -1, so the
+// fused epilogue keeps its global value.  This is exact, not approximate, while cg2d_b and
+// the first guess cg2d_x are 0.0 on those points, which holds by induction over the steps:
+//   * cg2d_b: sfp_rhs_column (common.h) sums the fluxes through the point's faces, all 0.0
+//     with the faces closed, the fresh-water term, masked by maskInC (0 on a dry column),
+//     and the free-surface term, a multiple of etaH (etaN without exactConserv);
+//   * cg2d_x, the first guess, is Bo_surf*etaN there; after the solve the epilogue (or
+//     k_exch_eta) sets etaN = recip_Bo*cg2d_x, 0.0 where cg2d_x stayed 0.0;
+//   * etaH: UPDATE_ETAH (k_corr_cont, k_calc_r_star) adds the masked divergence of the
+//     transports through the same closed faces to etaN: 0.0 again.
+// So the invariant can only be broken from outside: eta loaded from the host (checked by
+// mgcm_init and mgcm_put*, land_eta_check) or b / x handed to mgcm_cg2d.  The solver's
+// prologue scans the left-out points on every solve and records numIters = -1 on a
+// non-zero (k_cg2d_bxy), which mgcm_cg2d answers by solving again on the full tables and a
+// step reports as an error: a broken invariant is never a silently different answer.
+//
+// Selection: the first geometry of the preference list that the grid tiles into and that
+// fits its thread count -- with every block where the full count fits (tables as without
+// compaction), with the all-land blocks left out only where the full count does not fit
+// but the kept count does.  MGCM_CG2D_BXY=<BX>x<BY>x<NT> (or the variant's index) forces a
+// geometry; MGCM_CG2D_COMPACT=0 never leaves blocks out, =1 leaves them out wherever there
+// are any.  After a broken invariant (noCompact) neither switch applies: the full tables of
+// the first two geometries, as before compaction existed.
+struct BxyChoice {
+  int var = -1, bx = 0, by = 0, nt = 0;   // the geometry (kernels_solve.hip CGX[]); var -1: none fits
+  int nBlk = 0;                           // blocks in the tables
+  bool compacted = false;                 // the all-land blocks are left out
+  int Nx = 0;
+  std::vector<char> dry;                  // [global (J-1)*Nx + (I-1)]: the point may be left out; empty: no scan
+  bool block_dry(int I0, int J0) const { return block_dry(I0, J0, bx, by); }
+  bool block_dry(int I0, int J0, int bx_, int by_) const {
+    if (dry.empty()) return false;
+    for (int b = 0; b < by_; b++)
+      for (int a = 0; a < bx_; a++)
+        if (!dry[(size_t)(J0 + b - 1) * Nx + (I0 + a - 1)]) return false;
+    return true;
   }
-  // BX x BY blocks (k_cg2d_bxy), same global-index construction; the first geometry of
-  // the preference list the grid tiles into
-  //
-  // Land-block compaction.  A block is left out of the tables when every point of it is a dry
-  // column with all four faces closed at every level -- decided from the static arrays
-  // INI_CG2D / UPDATE_CG2D build aW2d / aS2d from (h0FacW / h0FacS under the non-linear free
-  // surface, else hFacW / hFacS) and from hFacC.  Only the kept blocks are numbered; a left-out
-  // point's slot is the ZERO slot, so its neighbours read 0.0, and its slot2 is -1, so the
-  // fused epilogue keeps its global value.  This is exact, not approximate, while cg2d_b and
-  // the first guess cg2d_x are 0.0 on those points, which holds by induction over the steps:
-  //   * cg2d_b: sfp_rhs_column (common.h) sums the fluxes through the point's faces, all 0.0
-  //     with the faces closed, the fresh-water term, masked by maskInC (0 on a dry column),
-  //     and the free-surface term, a multiple of etaH (etaN without exactConserv);
-  //   * cg2d_x, the first guess, is Bo_surf*etaN there; after the solve the epilogue (or
-  //     k_exch_eta) sets etaN = recip_Bo*cg2d_x, 0.0 where cg2d_x stayed 0.0;
-  //   * etaH: UPDATE_ETAH (k_corr_cont, k_calc_r_star) adds the masked divergence of the
-  //     transports through the same closed faces to etaN: 0.0 again.
-  // So the invariant can only be broken from outside: eta loaded from the host (checked by
-  // mgcm_init and mgcm_put*, land_eta_check) or b / x handed to mgcm_cg2d.  The solver's
-  // prologue scans the left-out points on every solve and records numIters = -1 on a
-  // non-zero (k_cg2d_bxy), which mgcm_cg2d answers by solving again on the full tables and a
-  // step reports as an error: a broken invariant is never a silently different answer.
-  //
-  // Selection: the first geometry of the preference list that the grid tiles into and that
-  // fits its thread count -- with every block where the full count fits (tables as without
-  // compaction), with the all-land blocks left out only where the full count does not fit
-  // but the kept count does.  MGCM_CG2D_BXY=<BX>x<BY>x<NT> (or the variant's index) forces a
-  // geometry; MGCM_CG2D_COMPACT=0 never leaves blocks out, =1 leaves them out wherever there
-  // are any.  After a broken invariant (noCompact) neither switch applies: the full tables of
-  // the first two geometries, as before compaction existed.
-  m->nBlkX = 0;
-  int BX = 0, BY = 0, NT = 0, nBx = 0;
-  m->bxyVar = -1;
-  m->h_dropG.clear();
-  m->nDropBlk = 0;
-  if (m->d_dropG) { (void)hipFree(m->d_dropG); m->d_dropG = nullptr; }
+};
+// A grid of more points than this gets no single-workgroup tables at all, whatever its land.
+// It was the capacity of the generic one-workgroup kernel (retired) and is kept so that no
+// grid's selection changes: lifting it would let large, mostly-land grids compact into
+// k_cg2d_bxy, a change to measure on its own.
+constexpr int CG2D_ONE_WG_MAX_POINTS = 8 * 1024;
+
+static int choose_bxy(mgcm_model *m, BxyChoice &c) {
+  const Dims &d = m->d;
+  c = BxyChoice{};
+  if (m->nPts > CG2D_ONE_WG_MAX_POINTS) return 0;
+  const int Nx = d.sNx * d.nSx, Ny = d.sNy * d.nSy;
+  c.Nx = Nx;
+  // variants of kernels_solve.hip CGX[]: 3x2x512 first, the measured order (DESIGN.md "CG2D
+  // on one CU", profiles/r07/cg2d_compact/); 3x4x256 (variant 2) fits no grid that 3x2x512
+  // does not -- every 3x4 block is two 3x2 blocks -- and is reached by MGCM_CG2D_BXY only
+  std::vector<int> pref = m->noCompact ? std::vector<int>{0, 1} : std::vector<int>{3, 0, 1};
+  const char *envG = m->noCompact ? nullptr : getenv("MGCM_CG2D_BXY");
+  const bool isForced = envG && *envG;
+  if (isForced) {
+    int forced = -1, fx = 0, fy = 0, ft = 0;
+    if (sscanf(envG, "%dx%dx%d", &fx, &fy, &ft) == 3) {
+      for (int v = 0; v < cg2d_bxy_variants(); v++) {
+        int bx, by, nt;
+        cg2d_bxy_geometry(v, &bx, &by, &nt);
+        if (bx == fx && by == fy && nt == ft) forced = v;
+      }
+    } else if (envG[0] >= '0' && envG[0] <= '9' && atoi(envG) < cg2d_bxy_variants())
+      forced = atoi(envG);
+    if (forced < 0) return set_err("build_nbr: MGCM_CG2D_BXY=%s names no k_cg2d_bxy geometry", envG);
+    pref.assign(1, forced);
+  }
+  if (!m->latlonTopology || getenv("MGCM_CG2D_NOBLOCKED")) return 0;
   const char *envC = m->noCompact ? nullptr : getenv("MGCM_CG2D_COMPACT");
   const int compactMode = m->noCompact ? 0 : (envC ? (atoi(envC) != 0 ? 2 : 0) : 1);   // 0 off, 1 where needed, 2 always
-  const bool blocked = m->latlonTopology && !getenv("MGCM_CG2D_NOBLOCKED");
-  // dry[global (J-1)*Nx + (I-1)]: the point may be left out
-  std::vector<char> dry;
-  auto gpt0 = [&](int I, int J, int &i, int &j, int &t) {
-    const int bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
-    t = bj * d.nSx + bi; i = (I - 1) % d.sNx + 1; j = (J - 1) % d.sNy + 1;
-  };
-  if (blocked && compactMode > 0) {
+  if (compactMode > 0) {
     const bool nl = m->p.nonlinFreeSurf > 0;
     const size_t n3 = (size_t)d.n3 * d.nTiles;
     std::vector<double> hW(n3), hS(n3), hC(n3);
     HIPCHK(hipMemcpy(hW.data(), nl ? m->f.h0FacW : m->f.hFacW, n3 * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hS.data(), nl ? m->f.h0FacS : m->f.hFacS, n3 * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hC.data(), nl ? m->f.h0FacC : m->f.hFacC, n3 * sizeof(double), hipMemcpyDeviceToHost));
-    dry.assign((size_t)Nx * Ny, 0);
+    c.dry.assign((size_t)Nx * Ny, 0);
     for (int J = 1; J <= Ny; J++)
       for (int I = 1; I <= Nx; I++) {
         int i, j, t;
-        gpt0(I, J, i, j, t);
+        tile_point(d, I, J, i, j, t);
         bool closed = true;
         for (int k = 1; k <= d.Nr && closed; k++)
           closed = hC[MG_I3(d, i, j, k, t)] == 0.0 && hW[MG_I3(d, i, j, k, t)] == 0.0 &&
                    hW[MG_I3(d, i + 1, j, k, t)] == 0.0 && hS[MG_I3(d, i, j, k, t)] == 0.0 &&
                    hS[MG_I3(d, i, j + 1, k, t)] == 0.0;
-        dry[(size_t)(J - 1) * Nx + (I - 1)] = closed;
+        c.dry[(size_t)(J - 1) * Nx + (I - 1)] = closed;
       }
   }
-  auto blockDry = [&](int I0, int J0, int bx, int by) {
-    if (dry.empty()) return false;
-    for (int b = 0; b < by; b++)
-      for (int a = 0; a < bx; a++)
-        if (!dry[(size_t)(J0 + b - 1) * Nx + (I0 + a - 1)]) return false;
-    return true;
-  };
-  bool compacted = false;
-  {
-    // variants of kernels_solve.hip CGX[]: 3x2x512 first, the measured order (DESIGN.md "CG2D
-    // on one CU", profiles/r07/cg2d_compact/); 3x4x256 (variant 2) fits no grid that 3x2x512
-    // does not -- every 3x4 block is two 3x2 blocks -- and is reached by MGCM_CG2D_BXY only
-    static const int prefNew[] = {3, 0, 1}, prefOld[] = {0, 1};
-    std::vector<int> pref;
-    int forced = -1;
-    const char *envG = m->noCompact ? nullptr : getenv("MGCM_CG2D_BXY");
-    if (envG && *envG) {
-      int fx = 0, fy = 0, ft = 0;
-      if (sscanf(envG, "%dx%dx%d", &fx, &fy, &ft) == 3) {
-        for (int v = 0; v < cg2d_bxy_variants(); v++) {
-          int bx, by, nt;
-          cg2d_bxy_geometry(v, &bx, &by, &nt);
-          if (bx == fx && by == fy && nt == ft) forced = v;
-        }
-      } else if (envG[0] >= '0' && envG[0] <= '9' && atoi(envG) < cg2d_bxy_variants())
-        forced = atoi(envG);
-      if (forced < 0) return set_err("build_nbr: MGCM_CG2D_BXY=%s names no k_cg2d_bxy geometry", envG);
-      pref.push_back(forced);
-    } else if (m->noCompact)
-      pref.assign(prefOld, prefOld + sizeof(prefOld) / sizeof(int));
-    else
-      pref.assign(prefNew, prefNew + sizeof(prefNew) / sizeof(int));
-    for (int v : pref) {
-      int bx, by, nt;
-      if (cg2d_bxy_geometry(v, &bx, &by, &nt)) continue;
-      const int n = (Nx % bx == 0 && Ny % by == 0) ? (Nx / bx) * (Ny / by) : 0;
-      if (n == 0) continue;
-      int nDry = 0;
-      if (blocked && compactMode > 0)
-        for (int J0 = 1; J0 <= Ny; J0 += by)
-          for (int I0 = 1; I0 <= Nx; I0 += bx) nDry += blockDry(I0, J0, bx, by) ? 1 : 0;
-      if (n <= nt && !(compactMode == 2 && nDry > 0)) { m->bxyVar = v; BX = bx; BY = by; NT = nt; nBx = n; break; }
-      if (nDry > 0 && n - nDry > 0 && n - nDry <= nt) {
-        m->bxyVar = v; BX = bx; BY = by; NT = nt; nBx = n - nDry; compacted = true;
-        break;
-      }
+  for (int v : pref) {
+    int bx, by, nt;
+    if (cg2d_bxy_geometry(v, &bx, &by, &nt)) continue;
+    const int n = (Nx % bx == 0 && Ny % by == 0) ? (Nx / bx) * (Ny / by) : 0;
+    if (n == 0) continue;
+    int nDry = 0;
+    for (int J0 = 1; J0 <= Ny; J0 += by)
+      for (int I0 = 1; I0 <= Nx; I0 += bx) nDry += c.block_dry(I0, J0, bx, by) ? 1 : 0;
+    const bool full = n <= nt && !(compactMode == 2 && nDry > 0);
+    if (full || (nDry > 0 && n - nDry > 0 && n - nDry <= nt)) {
+      c.var = v; c.bx = bx; c.by = by; c.nt = nt;
+      c.nBlk = full ? n : n - nDry;
+      c.compacted = !full;
+      return 0;
     }
-    if (forced >= 0 && blocked && m->bxyVar < 0)
-      return set_err("build_nbr: the grid does not fit the k_cg2d_bxy geometry MGCM_CG2D_BXY=%s", envG);
   }
-  if (blocked && m->bxyVar >= 0) {
-    const int NPT = BX * BY, NB = 2 * (BX + BY);
-    const unsigned Z = (unsigned)(NPT * NT);
-    // LDS slot of an interior point: point-in-block major, block minor (p*NT + block),
-    // so that consecutive threads touch consecutive doubles (no LDS bank conflicts)
-    std::vector<unsigned> slotOf((size_t)m->nPts, Z);
-    {
-      int qb = 0;
-      for (int J0 = 1; J0 <= Ny; J0 += BY)
-        for (int I0 = 1; I0 <= Nx; I0 += BX) {
-          const bool drop = compacted && blockDry(I0, J0, BX, BY);
-          for (int b = 0; b < BY; b++)
-            for (int a = 0; a < BX; a++) {
-              const int I = I0 + a, J = J0 + b, bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
-              const int t = bj * d.nSx + bi, i = (I - 1) % d.sNx + 1, j = (J - 1) % d.sNy + 1;
-              if (drop) m->h_dropG.push_back((int)MG_I2(d, i, j, t));
-              else slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)] = (unsigned)((b * BX + a) * NT + qb);
-            }
-          if (drop) m->nDropBlk++;
-          else qb++;
-        }
-    }
-    auto cmp = [&](long g) -> unsigned {
-      unsigned c = compact(g);
-      return c == ZERO ? Z : slotOf[c];
-    };
-    auto nbv = [&](int i, int j, int t) -> unsigned {
-      long g = MG_I2(d, i, j, t);
-      if (i < 1 || i > d.sNx || j < 1 || j > d.sNy) g = srcOf[g];
-      return cmp(g);
-    };
-    auto gpt = [&](int I, int J, int &i, int &j, int &t) {
-      const int bi = (I - 1) / d.sNx, bj = (J - 1) / d.sNy;
-      t = bj * d.nSx + bi; i = (I - 1) % d.sNx + 1; j = (J - 1) % d.sNy + 1;
-    };
-    std::vector<unsigned> nbx((size_t)(NB / 2) * NT, Z | (Z << 16));
-    std::vector<int> blkx((size_t)NPT * NT, (int)MG_I2(d, 1, 1, 0));
-    int q = 0;
-    for (int J0 = 1; J0 <= Ny; J0 += BY)
-      for (int I0 = 1; I0 <= Nx; I0 += BX) {
-        if (compacted && blockDry(I0, J0, BX, BY)) continue;
-        std::vector<int> ii(NPT), jj(NPT), tt(NPT);
-        for (int b = 0; b < BY; b++)
-          for (int a = 0; a < BX; a++) {
-            gpt(I0 + a, J0 + b, ii[b * BX + a], jj[b * BX + a], tt[b * BX + a]);
-            blkx[(size_t)NPT * q + b * BX + a] = (int)MG_I2(d, ii[b * BX + a], jj[b * BX + a], tt[b * BX + a]);
-          }
-        std::vector<unsigned> v(NB);
-        for (int b = 0; b < BY; b++) {
-          const int w = b * BX, e = b * BX + BX - 1;
-          v[b] = nbv(ii[w] - 1, jj[w], tt[w]);
-          v[BY + b] = nbv(ii[e] + 1, jj[e], tt[e]);
-        }
+  if (isForced)
+    return set_err("build_nbr: the grid does not fit the k_cg2d_bxy geometry MGCM_CG2D_BXY=%s", envG);
+  return 0;
+}
+
+// no k_cg2d_bxy tables: nothing is left out, so the land guards (land_eta_check, mgcm_cg2d) rest
+static void clear_bxy(mgcm_model *m) {
+  m->nBlkX = 0;
+  m->bxyVar = -1;
+  m->h_dropG.clear();
+  m->nDropBlk = 0;
+  if (m->d_dropG) { (void)hipFree(m->d_dropG); m->d_dropG = nullptr; }
+}
+
+static int build_bxy(mgcm_model *m, const BxyChoice &c) {
+  const Dims &d = m->d;
+  clear_bxy(m);
+  const std::vector<long> srcOf = halo_sources(m);
+  const int Nx = d.sNx * d.nSx, Ny = d.sNy * d.nSy;
+  const int BX = c.bx, BY = c.by, NT = c.nt, NPT = BX * BY, NB = 2 * (BX + BY);
+  const unsigned Z = (unsigned)(NPT * NT);   // the ZERO slot
+  // LDS slot of an interior point: point-in-block major, block minor (p*NT + block),
+  // so that consecutive threads touch consecutive doubles (no LDS bank conflicts)
+  std::vector<unsigned> slotOf((size_t)m->nPts, Z);
+  auto compact = [&](int i, int j, int t) { return (size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1); };
+  int qb = 0;
+  for (int J0 = 1; J0 <= Ny; J0 += BY)
+    for (int I0 = 1; I0 <= Nx; I0 += BX) {
+      const bool drop = c.compacted && c.block_dry(I0, J0);
+      for (int b = 0; b < BY; b++)
         for (int a = 0; a < BX; a++) {
-          const int so = a, no = (BY - 1) * BX + a;
-          v[2 * BY + a] = nbv(ii[so], jj[so] - 1, tt[so]);
-          v[2 * BY + BX + a] = nbv(ii[no], jj[no] + 1, tt[no]);
+          int i, j, t;
+          tile_point(d, I0 + a, J0 + b, i, j, t);
+          if (drop) m->h_dropG.push_back((int)MG_I2(d, i, j, t));
+          else slotOf[compact(i, j, t)] = (unsigned)((b * BX + a) * NT + qb);
         }
-        for (int k = 0; k < NB / 2; k++) nbx[(size_t)(NB / 2) * q + k] = v[2 * k] | (v[2 * k + 1] << 16);
-        q++;
-      }
-    // the epilogue's EXCH_XY_RL(cg2d_x): every 2-D point's value is the slot of itself
-    // (interior) or of its interior source (halo), -1 where neither (kept as it is)
-    std::vector<int> slot2((size_t)d.n2 * d.nTiles, -1);
-    for (int J = 1; J <= Ny; J++)
-      for (int I = 1; I <= Nx; I++) {
-        int i, j, t;
-        gpt(I, J, i, j, t);
-        const unsigned sl = slotOf[(size_t)t * d.sNx * d.sNy + (size_t)(j - 1) * d.sNx + (i - 1)];
-        slot2[(size_t)MG_I2(d, i, j, t)] = sl == Z ? -1 : (int)sl;   // -1: a point of a left-out block
-      }
-    for (size_t g = 0; g < slot2.size(); g++)
-      if (srcOf[g] >= 0) slot2[g] = slot2[(size_t)srcOf[g]];
-    if (m->d_slot2) (void)hipFree(m->d_slot2);
-    HIPCHK(hipMalloc(&m->d_slot2, slot2.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(m->d_slot2, slot2.data(), slot2.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (m->d_nbx) (void)hipFree(m->d_nbx);
-    if (m->d_blkx) (void)hipFree(m->d_blkx);
-    HIPCHK(hipMalloc(&m->d_nbx, nbx.size() * sizeof(unsigned)));
-    HIPCHK(hipMemcpy(m->d_nbx, nbx.data(), nbx.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&m->d_blkx, blkx.size() * sizeof(int)));
-    HIPCHK(hipMemcpy(m->d_blkx, blkx.data(), blkx.size() * sizeof(int), hipMemcpyHostToDevice));
-    m->nBlkX = nBx;
-    if (!m->h_dropG.empty()) {
-      HIPCHK(hipMalloc(&m->d_dropG, m->h_dropG.size() * sizeof(int)));
-      HIPCHK(hipMemcpy(m->d_dropG, m->h_dropG.data(), m->h_dropG.size() * sizeof(int), hipMemcpyHostToDevice));
-      if (!m->h_guard) {
-        HIPCHK(hipHostMalloc((void **)&m->h_guard, 64, hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void **)&m->d_guard, m->h_guard, 0));
-      }
-      *m->h_guard = 0;
+      if (drop) m->nDropBlk++;
+      else qb++;
     }
+  // slot of the value found at (i, j, t), through the halo map
+  auto slot = [&](int i, int j, int t) -> unsigned {
+    const long cp = value_point(d, srcOf, i, j, t);
+    return cp < 0 ? Z : slotOf[cp];
+  };
+  std::vector<unsigned> nbx((size_t)(NB / 2) * NT, Z | (Z << 16));
+  std::vector<int> blkx((size_t)NPT * NT, (int)MG_I2(d, 1, 1, 0));
+  int q = 0;
+  for (int J0 = 1; J0 <= Ny; J0 += BY)
+    for (int I0 = 1; I0 <= Nx; I0 += BX) {
+      if (c.compacted && c.block_dry(I0, J0)) continue;
+      std::vector<int> ii(NPT), jj(NPT), tt(NPT);
+      for (int b = 0; b < BY; b++)
+        for (int a = 0; a < BX; a++) {
+          tile_point(d, I0 + a, J0 + b, ii[b * BX + a], jj[b * BX + a], tt[b * BX + a]);
+          blkx[(size_t)NPT * q + b * BX + a] = (int)MG_I2(d, ii[b * BX + a], jj[b * BX + a], tt[b * BX + a]);
+        }
+      // out-of-block neighbours, through each boundary point's own halo map
+      std::vector<unsigned> v(NB);
+      for (int b = 0; b < BY; b++) {
+        const int w = b * BX, e = b * BX + BX - 1;
+        v[b] = slot(ii[w] - 1, jj[w], tt[w]);
+        v[BY + b] = slot(ii[e] + 1, jj[e], tt[e]);
+      }
+      for (int a = 0; a < BX; a++) {
+        const int so = a, no = (BY - 1) * BX + a;
+        v[2 * BY + a] = slot(ii[so], jj[so] - 1, tt[so]);
+        v[2 * BY + BX + a] = slot(ii[no], jj[no] + 1, tt[no]);
+      }
+      for (int k = 0; k < NB / 2; k++) nbx[(size_t)(NB / 2) * q + k] = v[2 * k] | (v[2 * k + 1] << 16);
+      q++;
+    }
+  // the epilogue's EXCH_XY_RL(cg2d_x): every 2-D point's value is the slot of itself
+  // (interior) or of its interior source (halo), -1 where neither (kept as it is)
+  std::vector<int> slot2((size_t)d.n2 * d.nTiles, -1);
+  for (int J = 1; J <= Ny; J++)
+    for (int I = 1; I <= Nx; I++) {
+      int i, j, t;
+      tile_point(d, I, J, i, j, t);
+      const unsigned sl = slotOf[compact(i, j, t)];
+      slot2[(size_t)MG_I2(d, i, j, t)] = sl == Z ? -1 : (int)sl;   // -1: a point of a left-out block
+    }
+  for (size_t g = 0; g < slot2.size(); g++)
+    if (srcOf[g] >= 0) slot2[g] = slot2[(size_t)srcOf[g]];
+  if (table_upload(m->d_slot2, slot2) || table_upload(m->d_nbx, nbx) || table_upload(m->d_blkx, blkx)) return -1;
+  m->bxyVar = c.var;
+  m->nBlkX = c.nBlk;
+  if (!m->h_dropG.empty()) {
+    if (table_upload(m->d_dropG, m->h_dropG)) return -1;
+    if (!m->h_guard) {
+      HIPCHK(hipHostMalloc((void **)&m->h_guard, 64, hipHostMallocMapped));
+      HIPCHK(hipHostGetDevicePointer((void **)&m->d_guard, m->h_guard, 0));
+    }
+    *m->h_guard = 0;
   }
   return 0;
 }
@@ -754,7 +718,6 @@ static int mwg_block_realloc(mgcm_model *m, int mem, bool sys);
 static int build_mwg(mgcm_model *m) {
   for (void *q : m->mwgAllocs) (void)hipFree(q);
   m->mwgAllocs.clear();
-  m->useMwg = false;
   const Dims &d = m->d;
   int NT, OPT, RPT;
   cg2d_mwg_geometry(&NT, &OPT, &RPT);
@@ -886,7 +849,7 @@ static int build_mwg(mgcm_model *m) {
   T.exclusive = 0;
   T.partsPerTile = (d.t0 == 0 && d.nT == d.nTiles) ? nPartsTile : 0;   // part ranges: whole-domain tables only
   // cg2dRefOrder: the sums chained along each tile's parts, then over the tiles (k_cg2d_mwg<.., REF>)
-  T.ref = m->p.cg2dRefOrder ? 1 : 0;
+  T.ref = m->solver == Cg2dSolver::MwgRef ? 1 : 0;
   T.nTiles = d.nTiles;
   if (T.ref && T.partsPerTile <= 0)
     return set_err("mgcm_init: cg2dRefOrder in the multi-workgroup CG2D needs the whole domain's tiles, not the tile "
@@ -913,7 +876,6 @@ static int build_mwg(mgcm_model *m) {
   T.xs = T.part + partGr;
   T.refc = T.ref ? T.xs + (size_t)nExp * 4 : nullptr;
   T.hsBytes = hs;
-  m->useMwg = true;
   // The hand-off block's memory: where the parts spread over the XCDs (not pinned), uncached
   // device memory -- a granule store is then visible to the other XCDs' polls without an L2
   // round of its own: LLC-90 1.591 ms/step against 1.688 with the coarse-grained block, 117
@@ -1053,8 +1015,6 @@ void mgcm_destroy(mgcm_model *m) {
   if (m->d_tileInfo) hipFree(m->d_tileInfo);
   if (m->d_nbr) hipFree(m->d_nbr);
   if (m->d_gofs) hipFree(m->d_gofs);
-  if (m->d_nb4) hipFree(m->d_nb4);
-  if (m->d_blk) hipFree(m->d_blk);
   if (m->d_nbx) hipFree(m->d_nbx);
   if (m->d_blkx) hipFree(m->d_blkx);
   if (m->d_slot2) hipFree(m->d_slot2);
@@ -1148,26 +1108,25 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
       return NAN;
     return it;
   }
-  // 6: k_cg2d_mwg in the reference order (cg2dRefOrder past one workgroup), 5: k_cg2d_block in the reference order
-  // (cg2dRefOrder), 4: k_cg2d_mwg, 3: k_cg2d_bxy, 2: k_cg2d_blk2, 1: k_cg2d_block
-  if (!strcmp(name, "cg2dKernel"))
-    return m->p.cg2dRefOrder ? (m->useMwg ? 6.0 : 5.0) : m->useMwg ? 4.0 : m->nBlkX > 0 ? 3.0 : (m->nBlk > 0 ? 2.0 : 1.0);
-  if (!strcmp(name, "cg2dParts")) return m->useMwg ? (double)m->mwg.G : 1.0;
+  // 3: k_cg2d_bxy, 4: k_cg2d_mwg, 5: k_cg2d_block (reference order), 6: k_cg2d_mwg in the
+  // reference order; 1 and 2 are retired (Cg2dSolver)
+  if (!strcmp(name, "cg2dKernel")) return (double)(int)m->solver;
+  if (!strcmp(name, "cg2dParts")) return m->useMwg() ? (double)m->mwg.G : 1.0;
   // 1 when the multi-workgroup solve's parts are placed on one XCD (one L2: ~1 us hand-offs)
-  if (!strcmp(name, "cg2dPinned")) return m->useMwg ? (double)m->mwg.pinned : 0.0;
+  if (!strcmp(name, "cg2dPinned")) return m->useMwg() ? (double)m->mwg.pinned : 0.0;
   // THERMODYNAMICS on the second stream: 1 on, 0 off; -1 while the graph path is still timing
   // both (ovlMsOn / ovlMsOff: ovl_trial's event times of the two graphs, 8 steps each)
   if (!strcmp(name, "overlap")) return (m->ovlAuto && !m->ovlDecided) ? -1.0 : (m->overlap ? 1.0 : 0.0);
   if (!strcmp(name, "ovlMsOn")) return m->ovlMs[1];
   if (!strcmp(name, "ovlMsOff")) return m->ovlMs[0];
   if (!strcmp(name, "cg2dBxyVariant")) return (double)m->bxyVar;
-  if (!strcmp(name, "cg2dDroppedBlocks")) return (double)(m->nBlkX > 0 ? m->nDropBlk : 0);
+  if (!strcmp(name, "cg2dDroppedBlocks")) return (double)(m->solver == Cg2dSolver::Bxy ? m->nDropBlk : 0);
   // the launch layout of the last FORWARD_STEP built (one_step): bit 0 THERMODYNAMICS folded
   // into DYNAMICS' grids (k_dt_l1/l2/l3), 1 DO_OCEANIC_PHYS + CALC_PHI_HYD in one pass,
   // 2 the tracers on the second stream, 3 joined only before the correction step
   if (!strcmp(name, "stepLayout")) return (double)m->stepLayout;
   // whether the selected kernel solves with fused multiply-adds (k_cg2d_bxy honours cg2dUseFMA)
-  if (!strcmp(name, "cg2dFMA")) return (!m->p.cg2dRefOrder && !m->useMwg && m->nBlkX > 0 && m->p.cg2dUseFMA) ? 1.0 : 0.0;
+  if (!strcmp(name, "cg2dFMA")) return (m->solver == Cg2dSolver::Bxy && m->p.cg2dUseFMA) ? 1.0 : 0.0;
   for (auto &pd : PARAMS)
     if (!strcmp(pd.name, name)) {
       const char *ptr = reinterpret_cast<const char *>(&m->p) + pd.off;
@@ -1393,11 +1352,32 @@ int mgcm_init(mgcm_model *m) {
     m->allocs.push_back(m->snapH);
   }
   if (upload_halo(m)) return -1;
+  // The CG2D solver, selected here and nowhere else:
+  //   * cg2dRefOrder (parity runs on the reference's own tiling): the reference's summation
+  //     order, in k_cg2d_block where the grid fits one workgroup, else in k_cg2d_mwg<.., REF>;
+  //   * k_cg2d_bxy on a lat-lon grid that fits one of its geometries (choose_bxy);
+  //   * otherwise, or with cg2dForceMwg (the tile-sharded device CG2D runs its parts in several
+  //     processes), the multi-workgroup k_cg2d_mwg.  A generic point-per-thread kernel in one
+  //     workgroup once took the grids k_cg2d_bxy does not; it measured 12.7 against 4.2
+  //     us/iteration on the cube and was superseded in round 3.
   m->noCompact = false;
-  if (build_nbr(m)) return -1;
+  m->nPts = m->d.nTiles * m->d.sNx * m->d.sNy;
+  BxyChoice bxy;
+  if (choose_bxy(m, bxy)) return -1;
+  if (m->p.cg2dRefOrder) {
+    if (m->p.useSRCGSolver) return set_err("mgcm_init: cg2dRefOrder with useSRCGSolver not implemented");
+    m->solver = m->nPts > cg2d_ref_max_points() ? Cg2dSolver::MwgRef : Cg2dSolver::BlockRef;
+  } else
+    m->solver = (bxy.var < 0 || ext("cg2dForceMwg", 0.0) != 0.0) ? Cg2dSolver::Mwg : Cg2dSolver::Bxy;
+  if (m->p.useSRCGSolver && m->solver == Cg2dSolver::BlockRef)
+    return set_err("mgcm_init: useSRCGSolver (CG2D_SR) is implemented in the blocked single-workgroup and the "
+                   "multi-workgroup CG2D only");
+  clear_bxy(m);
+  if (m->solver == Cg2dSolver::Bxy ? build_bxy(m, bxy) : m->solver == Cg2dSolver::BlockRef ? build_block(m) : build_mwg(m))
+    return -1;
   if (!m->h_dropG.empty()) {
     // the state the fields were loaded with (a cold start, a pickup): eta must be 0.0 on the
-    // points the compacted tables leave out, else the full tables (build_nbr)
+    // points the compacted tables leave out, else the full tables (land_uncompact)
     const long n2a = m->d.n2 * m->d.nTiles;
     std::vector<double> eta((size_t)n2a);
     for (const char *nm : {"etaN", "etaH"}) {
@@ -1406,31 +1386,6 @@ int mgcm_init(mgcm_model *m) {
       if (land_eta_check(m, nm, eta.data(), n2a)) return -1;
     }
   }
-  // CG2D kernel: the single-workgroup blocked solvers on lat-lon grids that tile into their
-  // blocks; otherwise the multi-workgroup solver (the generic single-workgroup kernel measured
-  // 12.7 against 4.2 us/iteration on the cube, round 3)
-  m->useMwg = false;
-  // cg2dRefOrder (parity runs on the reference's own tiling): the reference's summation order in
-  // the generic single-workgroup kernel where the grid fits one workgroup, else in the
-  // multi-workgroup solver (k_cg2d_mwg<.., REF>)
-  if (m->p.cg2dRefOrder) {
-    if (m->p.useSRCGSolver) return set_err("mgcm_init: cg2dRefOrder with useSRCGSolver not implemented");
-    if (m->nPts > cg2d_ref_max_points()) {
-      m->nBlkX = 0;
-      m->nBlk = 0;
-      if (build_mwg(m)) return -1;
-    }
-  } else if ((m->nBlkX == 0 && m->nBlk == 0) ||
-             ext("cg2dForceMwg", 0.0) != 0.0) {
-    // cg2dForceMwg: the multi-workgroup solver on a grid the single-workgroup kernels would
-    // take (the tile-sharded device CG2D runs its parts in several processes)
-    m->nBlkX = 0;
-    m->nBlk = 0;
-    if (build_mwg(m)) return -1;
-  }
-  if (m->p.useSRCGSolver && !m->useMwg && m->nBlkX == 0)
-    return set_err("mgcm_init: useSRCGSolver (CG2D_SR) is implemented in the blocked single-workgroup and the "
-                   "multi-workgroup CG2D only");
   if ((m->p.viscA4D != 0.0 || m->p.viscA4Z != 0.0) && (m->d.OLx < 3 || m->d.OLy < 3))
     return set_err("mgcm_init: biharmonic viscosity needs OLx, OLy >= 3 (del2u of the halo ring)");
   const bool rstar = m->p.nonlinFreeSurf > 0;
@@ -1533,40 +1488,43 @@ int mgcm_init(mgcm_model *m) {
 // EXCH_XY_RL(cg2d_x) + etaN (k_exch_eta) inside the CG2D launch: the single-workgroup
 // blocked solver holds the whole solution, so its epilogue writes every point's value
 static bool cg2d_fuses_eta(const mgcm_model *m) {
-  return !m->p.cg2dRefOrder && !m->useMwg && m->nBlkX > 0 && m->d_slot2 && m->d.nT == m->d.nTiles;
+  return m->solver == Cg2dSolver::Bxy && m->d.nT == m->d.nTiles;
 }
 
 static hipError_t launch_cg2d(mgcm_model *m, int maxIters, int nIterMin, bool fuseEta = false) {
-  if (m->p.cg2dRefOrder && !m->useMwg)
-    return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
-                             m->stream);
-  if (m->useMwg) {
-    return launch_cg2d_mwg(m->d, m->p, m->f, m->mwg, maxIters, nIterMin, m->d_rec, m->d_ctr + 1, m->stream);
+  switch (m->solver) {
+    case Cg2dSolver::Bxy:
+      return launch_cg2d_bxy(m->bxyVar, m->d, m->p, m->f, m->d_nbx, m->d_blkx, m->nBlkX, maxIters, nIterMin, m->d_rec,
+                             m->d_ctr + 1, fuseEta ? m->d_slot2 : nullptr, m->d_srcOf, m->d_dropG, (int)m->h_dropG.size(),
+                             m->h_dropG.empty() ? nullptr : m->d_guard, m->stream);
+    case Cg2dSolver::BlockRef:
+      return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
+                               m->stream);
+    case Cg2dSolver::Mwg:
+    case Cg2dSolver::MwgRef:
+      return launch_cg2d_mwg(m->d, m->p, m->f, m->mwg, maxIters, nIterMin, m->d_rec, m->d_ctr + 1, m->stream);
   }
-  if (m->nBlkX > 0)
-    return launch_cg2d_bxy(m->bxyVar, m->d, m->p, m->f, m->d_nbx, m->d_blkx, m->nBlkX, maxIters, nIterMin, m->d_rec,
-                           m->d_ctr + 1, fuseEta ? m->d_slot2 : nullptr, m->d_srcOf, m->d_dropG, (int)m->h_dropG.size(),
-                           m->h_dropG.empty() ? nullptr : m->d_guard, m->stream);
-  if (m->nBlk > 0)
-    return launch_cg2d_blk2(m->d, m->p, m->f, m->d_nb4, m->d_blk, m->nBlk, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
-                            m->stream);
-  return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
-                           m->stream);
+  return hipErrorInvalidValue;
 }
 
-// The zero-on-land invariant of the compacted k_cg2d_bxy tables (build_nbr), on the host side.
+// The zero-on-land invariant of the compacted k_cg2d_bxy tables (choose_bxy), on the host side;
+// only the Bxy solver leaves blocks out (h_dropG), so only it comes here.
 // land_uncompact: the full tables of the geometry used before compaction existed, from now on;
-// the captured graphs hold the old tables' addresses and go.
+// the captured graphs hold the old tables' addresses and go.  The solver stays k_cg2d_bxy: a
+// grid whose full tables fit no geometry is an error.
 static int land_uncompact(mgcm_model *m) {
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipStreamSynchronize(m->stream));
   drop_graphs(m);
   m->noCompact = true;
-  if (build_nbr(m)) return -1;
+  BxyChoice bxy;
+  if (choose_bxy(m, bxy)) return -1;
   if (m->h_guard) *m->h_guard = 0;
-  if (m->nBlkX == 0 && m->nBlk == 0 && !m->p.cg2dRefOrder && !m->useMwg)
+  if (bxy.var < 0) {
+    clear_bxy(m);
     return set_err("land_uncompact: no single-workgroup CG2D fits this grid without leaving the all-land blocks out");
-  return 0;
+  }
+  return build_bxy(m, bxy);
 }
 // eta arriving from the host (n values of a 2-D field from its start): non-zero on a left-out point?
 static int land_eta_check(mgcm_model *m, const char *name, const double *host, long n) {
@@ -2221,7 +2179,7 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
 int mgcm_set_tile_range(mgcm_model *m, int t0, int nT) {
   if (t0 < 0 || nT < 1 || t0 + nT > m->d.nTiles)
     return set_err("mgcm_set_tile_range: tiles [%d, %d) outside [0, %d)", t0, t0 + nT, m->d.nTiles);
-  if (m->useMwg && m->mwg.ref && nT < m->d.nTiles)
+  if (m->solver == Cg2dSolver::MwgRef && nT < m->d.nTiles)
     return set_err("mgcm_set_tile_range: cg2dRefOrder in the multi-workgroup CG2D needs the whole domain's tiles, not the "
                    "tile range [%d, %d) of %d", t0, t0 + nT, m->d.nTiles);
   m->d.t0 = t0;
@@ -2311,7 +2269,7 @@ static int mwg_block_uncached(mgcm_model *m);
 // the whole domain: no sub-launch of a tile range, no hand-off block shared between processes
 // or models
 static int mwg_ref_refuse(const mgcm_model *m, const char *who) {
-  if (!m->useMwg || !m->mwg.ref) return 0;
+  if (m->solver != Cg2dSolver::MwgRef) return 0;
   return set_err("%s: cg2dRefOrder in the multi-workgroup CG2D runs the whole domain in one launch of one model "
                  "(no tile ranges, no shared hand-off block)", who);
 }
@@ -2335,7 +2293,7 @@ static int mwg_restart_epoch(mgcm_model *m, bool zeroBlock) {
 // first process exports by IPC and the others map; every granule access is then at system
 // scope.  The sums keep the single-launch order, so the solve is the 1-process solve.
 int mgcm_cg2d_shared_export(mgcm_model *m, void *handle) {
-  if (!m->useMwg || m->mwg.partsPerTile <= 0)
+  if (!m->useMwg() || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_shared_export: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
   if (mwg_ref_refuse(m, "mgcm_cg2d_shared_export")) return -1;
   HIPCHK(hipSetDevice(m->device));
@@ -2349,7 +2307,7 @@ int mgcm_cg2d_shared_export(mgcm_model *m, void *handle) {
 }
 
 int mgcm_cg2d_shared_import(mgcm_model *m, const void *handle) {
-  if (!m->useMwg || m->mwg.partsPerTile <= 0)
+  if (!m->useMwg() || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_shared_import: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
   if (mwg_ref_refuse(m, "mgcm_cg2d_shared_import")) return -1;
   HIPCHK(hipSetDevice(m->device));
@@ -2370,7 +2328,7 @@ int mgcm_cg2d_shared_import(mgcm_model *m, const void *handle) {
   return 0;
 }
 
-int mgcm_cg2d_shared_bytes(mgcm_model *m) { return m->useMwg ? (int)sizeof(hipIpcMemHandle_t) : -1; }
+int mgcm_cg2d_shared_bytes(mgcm_model *m) { return m->useMwg() ? (int)sizeof(hipIpcMemHandle_t) : -1; }
 
 // After a caller replays its own captured steps (ShardedModel.replay): the number of steps
 // the batch recorded, so mgcm_solve_stats finds them.
@@ -2466,7 +2424,7 @@ int mgcm_step_phase(mgcm_model *m, int phase) {
       TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream));
       return 0;
     case 10:  // the device CG2D over this process's parts (hand-off block shared by IPC)
-      if (!m->useMwg || m->mwg.partsPerTile <= 0)
+      if (!m->useMwg() || m->mwg.partsPerTile <= 0)
         return set_err("mgcm_step_phase(10): needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
       if (m->d.nT < m->d.nTiles && mwg_ref_refuse(m, "mgcm_step_phase(10) on a tile subset")) return -1;
       if (m->d.nT < m->d.nTiles && !m->mwg.sys)
@@ -2609,7 +2567,7 @@ long mgcm_halo_sources(mgcm_model *m, int t0, int nT, long *out, long cap) {
 // several GPUs one launch per GPU on one shared hand-off block (mgcm_cg2d_share).
 int mgcm_cg2d_tiles(mgcm_model *m, int t0, int nT) {
   if (check_ready(m)) return -1;
-  if (!m->useMwg || m->mwg.partsPerTile <= 0)
+  if (!m->useMwg() || m->mwg.partsPerTile <= 0)
     return set_err("mgcm_cg2d_tiles: needs the multi-workgroup CG2D on whole-domain tables (cg2dForceMwg)");
   if (t0 < 0 || nT < 1 || t0 + nT > m->d.nTiles) return set_err("mgcm_cg2d_tiles: bad tile range");
   if (nT < m->d.nTiles && mwg_ref_refuse(m, "mgcm_cg2d_tiles on a tile subset")) return -1;
@@ -2654,7 +2612,7 @@ static int mwg_block_uncached(mgcm_model *m) {
 // another GPU): the block becomes uncached device memory of the owner's GPU, m's launches map
 // it by peer access, and both poll at system scope.  m == owner prepares the owner only.
 int mgcm_cg2d_share(mgcm_model *m, mgcm_model *owner) {
-  if (!m->useMwg || !owner->useMwg || m->mwg.partsPerTile <= 0 || m->mwg.G != owner->mwg.G)
+  if (!m->useMwg() || !owner->useMwg() || m->mwg.partsPerTile <= 0 || m->mwg.G != owner->mwg.G)
     return set_err("mgcm_cg2d_share: both models need the same whole-domain multi-workgroup CG2D (cg2dForceMwg)");
   if (mwg_ref_refuse(m, "mgcm_cg2d_share") || mwg_ref_refuse(owner, "mgcm_cg2d_share")) return -1;
   HIPCHK(hipSetDevice(owner->device));
@@ -2843,41 +2801,42 @@ double mgcm_kernel_ms(mgcm_model *m, const char *name, int *launches) {
 // replacement), for the oracle to restate it: thread tid accumulates the per-point terms of
 // plan[p*NT + tid] (2-D flat offsets; -1 = padding) for p = 0..PPT-1 in order, starting from
 // 0.0; the NT thread partials are then combined by the pairwise tree the DPP row sums,
-// row broadcasts and the cross-wave row sum implement (block_sum / block_sum_nw: lanes
+// row broadcasts and the cross-wave slot tree implement (block_sum_nw: lanes
 // (2i, 2i+1), then pairs of pairs, ..., in thread order, zero-padded to a power of two).
 int mgcm_cg2d_sum_plan(mgcm_model *m, int *plan, long capacity, int *NT, int *PPT, int *NG) {
   if (!m->ready) return set_err("mgcm_cg2d_sum_plan: model not initialised");
-  int nt, ppt, ng = 1;
+  int nt = 0, ppt = 0, ng = 1;
   std::vector<int> tab;
-  if (m->useMwg) {
-    int rpt;
-    cg2d_mwg_geometry(&nt, &ppt, &rpt);
-    ng = m->mwg.G;
-    tab = m->mwgPlan;
-  } else if (m->nBlkX > 0) {
-    int BX, BY;
-    cg2d_bxy_geometry(m->bxyVar, &BX, &BY, &nt);
-    ppt = BX * BY;
-    std::vector<int> blkx((size_t)ppt * nt);
-    HIPCHK(hipMemcpy(blkx.data(), m->d_blkx, blkx.size() * sizeof(int), hipMemcpyDeviceToHost));
-    tab.assign((size_t)ppt * nt, -1);
-    for (int t = 0; t < m->nBlkX; t++)
-      for (int q = 0; q < ppt; q++) tab[(size_t)q * nt + t] = blkx[(size_t)ppt * t + q];
-  } else if (m->nBlk > 0) {
-    nt = 1024; ppt = 4;
-    std::vector<int> blk((size_t)4 * nt);
-    HIPCHK(hipMemcpy(blk.data(), m->d_blk, blk.size() * sizeof(int), hipMemcpyDeviceToHost));
-    tab.assign((size_t)4 * nt, -1);
-    for (int t = 0; t < m->nBlk; t++)
-      for (int q = 0; q < 4; q++) tab[(size_t)q * nt + t] = blk[(size_t)4 * t + q];
-  } else {
-    nt = 1024; ppt = cg2d_block_ppt(m->nPts);
-    std::vector<int> gofs((size_t)ppt * nt);
-    HIPCHK(hipMemcpy(gofs.data(), m->d_gofs, gofs.size() * sizeof(int), hipMemcpyDeviceToHost));
-    tab.assign((size_t)ppt * nt, -1);
-    for (int q = 0; q < ppt; q++)
-      for (int t = 0; t < nt; t++)
-        if (t + q * nt < m->nPts) tab[(size_t)q * nt + t] = gofs[(size_t)t + (size_t)q * nt];
+  switch (m->solver) {
+    case Cg2dSolver::Mwg:
+    case Cg2dSolver::MwgRef: {
+      int rpt;
+      cg2d_mwg_geometry(&nt, &ppt, &rpt);
+      ng = m->mwg.G;
+      tab = m->mwgPlan;
+      break;
+    }
+    case Cg2dSolver::Bxy: {
+      int BX, BY;
+      if (cg2d_bxy_geometry(m->bxyVar, &BX, &BY, &nt)) return set_err("mgcm_cg2d_sum_plan: no k_cg2d_bxy tables");
+      ppt = BX * BY;
+      std::vector<int> blkx((size_t)ppt * nt);
+      HIPCHK(hipMemcpy(blkx.data(), m->d_blkx, blkx.size() * sizeof(int), hipMemcpyDeviceToHost));
+      tab.assign((size_t)ppt * nt, -1);
+      for (int t = 0; t < m->nBlkX; t++)
+        for (int q = 0; q < ppt; q++) tab[(size_t)q * nt + t] = blkx[(size_t)ppt * t + q];
+      break;
+    }
+    case Cg2dSolver::BlockRef: {
+      nt = 1024; ppt = cg2d_block_ppt(m->nPts);
+      std::vector<int> gofs((size_t)ppt * nt);
+      HIPCHK(hipMemcpy(gofs.data(), m->d_gofs, gofs.size() * sizeof(int), hipMemcpyDeviceToHost));
+      tab.assign((size_t)ppt * nt, -1);
+      for (int q = 0; q < ppt; q++)
+        for (int t = 0; t < nt; t++)
+          if (t + q * nt < m->nPts) tab[(size_t)q * nt + t] = gofs[(size_t)t + (size_t)q * nt];
+      break;
+    }
   }
   *NT = nt;
   *PPT = ppt;

@@ -201,11 +201,14 @@ class Model:
         return plan[:nt.value * ppt.value * ng.value].copy(), nt.value, ppt.value, ng.value
 
     def cg2d_kernel(self):
-        """Which CG2D kernel mgcm_init selected: 'mwg' (multi-workgroup), 'bxy' (BX x BY points/thread),
-        'blk2' (2x2), 'block', or, summing in the reference's order (cg2dRefOrder), 'block_ref'
+        """Which CG2D solver mgcm_init selected: 'bxy' (one workgroup, BX x BY points/thread), 'mwg'
+        (multi-workgroup), or, summing in the reference's order (cg2dRefOrder), 'block_ref'
         (k_cg2d_block, up to one workgroup's points) and 'mwg_ref' (multi-workgroup, past that)."""
         k = lib().mgcm_get_param(self.h, b"cg2dKernel")
-        return {6.0: "mwg_ref", 5.0: "block_ref", 4.0: "mwg", 3.0: "bxy", 2.0: "blk2"}.get(k, "block")
+        names = {3.0: "bxy", 4.0: "mwg", 5.0: "block_ref", 6.0: "mwg_ref"}
+        if k not in names:
+            raise RuntimeError("cg2dKernel = %r names no CG2D solver" % (k,))
+        return names[k]
 
     def step_layout(self):
         """The launch layout of the last step built (mgcm_get_param 'stepLayout'): which

@@ -1,4 +1,4 @@
-"""Land-block compaction of the single-workgroup CG2D (k_cg2d_bxy, model.hip build_nbr): blocks
+"""Land-block compaction of the single-workgroup CG2D (k_cg2d_bxy, model.hip choose_bxy, build_bxy): blocks
 whose points are all dry columns with closed faces are left out of the solver's tables, which
 lets a grid fit a geometry of fewer threads; the zero-on-land invariant that makes this exact
 is checked where state enters from the host and by the solver itself.
@@ -17,7 +17,7 @@ from shapes import BOX_FIELDS, assert_bitexact_steps, box_rhs
 
 pytestmark = pytest.mark.gpu
 
-# k_cg2d_bxy's geometries, by name, and the default preference order (model.hip build_nbr)
+# k_cg2d_bxy's geometries, by name, and the default preference order (model.hip choose_bxy)
 GEOM = {"2x4x512": (2, 4, 512), "2x2x1024": (2, 2, 1024), "3x4x256": (3, 4, 256), "3x2x512": (3, 2, 512)}
 PREFERENCE = ("3x2x512", "2x4x512", "2x2x1024")
 
@@ -120,7 +120,7 @@ def blocks(dry, BX, BY):
 
 
 def policy(dry, preference=PREFERENCE, force=None, compact=None):
-    """(name, count of plan entries >= 0, compacted?) the selection of build_nbr gives: the first
+    """(name, count of plan entries >= 0, compacted?) the selection of choose_bxy gives: the first
     geometry of the list whose full block count fits its threads (every block kept) or, failing
     that, whose count without the all-dry blocks does; compact=1 leaves them out wherever there are
     any, compact=0 never."""

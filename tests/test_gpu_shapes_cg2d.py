@@ -5,7 +5,7 @@ reference-order k_cg2d_block at 1, 2 and 4 points per thread.
 
 The domain is shapes.box (a barotropic channel of free size with islands and varying
 depths).  Every case first asserts the kernel form it is there for -- worked out from
-build_nbr / build_mwg (csrc/model.hip) and written beside the case -- and then solves a
+choose_bxy / build_mwg (csrc/model.hip) and written beside the case -- and then solves a
 seeded right-hand side, compared with a dense float64 solve of the same operator
 (shapes.dense_cg2d_solution; pinned against the oracle by test_oracle_shapes.py):
   * iterations within 1 of the reference-order oracle's;
@@ -22,7 +22,9 @@ import shapes
 
 pytestmark = pytest.mark.gpu
 
-# How build_nbr / build_mwg decide (Nx, Ny the global size, nPts = Nx*Ny):
+# How choose_bxy / build_mwg decide (Nx, Ny the global size, nPts = Nx*Ny):
+#   k_cg2d_bxy 3x2 on 512 threads  where Nx % 3 == 0, Ny even and Nx/3 * Ny/2 <= 512, or as few
+#     once the all-land blocks are left out (test_gpu_cg2d_compact.py; no case here);
 #   k_cg2d_bxy 2x4 on 512 threads  where Nx % 2 == 0, Ny % 4 == 0 and Nx/2 * Ny/4 <= 512;
 #   k_cg2d_bxy 2x2 on 1024 threads where Nx, Ny even and Nx/2 * Ny/2 <= 1024;
 #   otherwise the multi-workgroup solver: 1024 threads x 1 point per part (cg2d_mwg_geometry);
@@ -72,6 +74,7 @@ def _assert_form(m, shape):
     from mitgcm_amd._lib import lib
     kernel, NT, PPT, sizes, pinned = CASES[shape]
     assert m.cg2d_kernel() == kernel, (shape, m.cg2d_kernel())
+    assert lib().mgcm_get_param(m.h, b"cg2dKernel") in (3.0, 4.0, 5.0, 6.0)   # 1 and 2 are retired
     plan, nt, ppt, ng = m.cg2d_sum_plan()
     got = [int(n) for n in (plan.reshape(ng, nt * ppt) >= 0).sum(axis=1)]
     assert (nt, ppt, got) == (NT, PPT, sizes), (shape, nt, ppt, got)
@@ -116,10 +119,15 @@ def test_box_cg2d_sr_mwg_vs_dense_solve(shape):
 @pytest.mark.parametrize("shape,ppt", list(REF_CASES.items()), ids=["ppt1", "ppt2", "ppt4"])
 def test_box_block_ref_4_steps_bitexact(shape, ppt):
     """4 steps with CG2D summed in the reference's order, bit-identical to the plain oracle."""
+    from mitgcm_amd._lib import lib
     from oracle.harness import oracle_from_config
     Nx, Ny = shape[:2]
     assert 1024 * (ppt // 2) < Nx * Ny <= 1024 * ppt
+
+    def after(m):   # no k_cg2d_bxy tables are built beside k_cg2d_block's: nothing is left out
+        assert lib().mgcm_get_param(m.h, b"cg2dDroppedBlocks") == 0
+
     kernel, parts, _ = shapes.assert_bitexact_steps(
         shapes.box_cfg(shape, cg2dRefOrder=1), 4, shapes.BOX_FIELDS,
-        oracle_factory=lambda cfg: oracle_from_config(shapes.box_cfg(shape)))
+        oracle_factory=lambda cfg: oracle_from_config(shapes.box_cfg(shape)), after=after)
     assert (kernel, parts) == ("block_ref", 1)
