@@ -10,6 +10,7 @@
 // source (srcOf, the EXCH map of the tile topology) inside the same pass, because
 // EXCH copies values that are computed by the same expression as the source's.
 #include "common.h"
+#include "phys.h"
 #include "ucg2d.h"
 
 namespace mgcm {
@@ -38,15 +39,19 @@ __device__ __forceinline__ double eta_exch(const Dims &d, const Fields &f, const
 // the neighbours it reads from eta_exch, the same values k_exch_etaH stores.  The only
 // cross-thread location both read and written is etaN at points neither interior nor
 // mapped, which is rewritten with the value it holds.
+// empNext (MG_FUSE_PIPE, with FUSE): the next step's DO_OCEANIC_PHYS ran earlier in this step
+// and left its EmPmR in EmPmRnext (phys.h); this pass, the step's last reader of EmPmR, moves
+// it over once it has formed PmEpR -- each thread its own point.
 template <bool FUSE>
 __device__ __forceinline__ void calc_r_star_body(const Dims &d, const Params &p, const Fields &f,
-                                                 const long *__restrict__ srcOf, int lb, int fromX) {
+                                                 const long *__restrict__ srcOf, int lb, int fromX, int empNext = 0) {
   const long q = (long)lb * blockDim.x + threadIdx.x;
   if (q >= d.n2 * d.nTiles) return;
   const int t = (int)(q / d.n2);
   if (t < d.t0 || t >= d.t0 + d.nT) return;
   if constexpr (FUSE) {   // k_exch_etaH (kernels_solve.hip), atInit = 0
     if (p.nonlinFreeSurf > 0 && p.useRealFreshWaterFlux) f.PmEpR[q] = -f.EmPmR[q];
+    if (empNext) f.EmPmR[q] = f.EmPmRnext[q];
     const double x = eta_exch(d, f, srcOf, q, fromX);
     f.etaHnm1[q] = f.etaH[q];
     f.etaN[q] = x;
@@ -102,9 +107,9 @@ __global__ void __launch_bounds__(256) k_calc_r_star(Dims d, Params p, Fields f,
 template <bool FUSE>
 __global__ void __launch_bounds__(256) k_rstar_exch(Dims d, Params p, Fields f, const long *__restrict__ srcOf, int nbR,
                                                     XFields x, const long *__restrict__ map, int nHalo, int *ctr, int nbX,
-                                                    int nzMax, int fromX) {
+                                                    int nzMax, int fromX, int empNext) {
   const int b = (int)blockIdx.x;
-  if (b < nbR) { calc_r_star_body<FUSE>(d, p, f, srcOf, b, fromX); return; }
+  if (b < nbR) { calc_r_star_body<FUSE>(d, p, f, srcOf, b, fromX, empNext); return; }
   const int r = b - nbR;
   exchange_multi_body(d, x, map, nHalo, ctr, r % nbX, (r / nbX) % nzMax, r / (nbX * nzMax));
 }
@@ -139,11 +144,19 @@ __global__ void __launch_bounds__(256) k_rstar_exmix(Dims d, Params p, Fields f,
 // nbPc > 0: the operator was built in an earlier launch of the step (opIn = 0) and UPDATE_CG2D's
 // preconditioner rides here, on the first nbPc logical blocks (ucg2d_p_point; the column
 // frame on the rest)
-template <bool SFP>
+// PH (MG_FUSE_PIPE): the next step's DO_OCEANIC_PHYS on the first nbPh logical blocks
+// (phys.h phys_hoist_body: it reads the new theta and salt, totPhiHyd, h0FacC*rStarFacC and
+// EmPmR, none of which this pass writes, and writes nothing this pass reads)
+template <bool SFP, bool PH>
 __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, Fields f, int nc, int opIn,
-                                                              const long *__restrict__ srcOf, int nbPc) {
+                                                              const long *__restrict__ srcOf, int nbPc,
+                                                              const int *iterPtr, int nbPh) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int lb = mg_xcd_block();
+  if constexpr (PH) {
+    if (lb < nbPh) { phys_hoist_body(d, p, f, iterPtr, srcOf, lb); return; }
+    lb -= nbPh;
+  }
   if (lb < nbPc) { ucg2d_p_point(d, p, f, srcOf, lb); return; }
   lb -= nbPc;
   MG_COLF_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, nc, lb)
@@ -222,7 +235,7 @@ hipError_t launch_calc_r_star(const Dims &d, const Params &p, const Fields &f, c
 }
 
 hipError_t launch_rstar_exch(const Dims &d, const Params &p, const Fields &f, const long *srcOf, bool fuseEtaH,
-                             const XFields &x, const long *map, int nHalo, int *ctr, hipStream_t s, int fromX) {
+                             const XFields &x, const long *map, int nHalo, int *ctr, hipStream_t s, int fromX, int empNext) {
   const long n = d.n2 * d.nTiles;
   const int nbR = (int)((n + 255) / 256);
   int nzMax = 1;
@@ -230,7 +243,7 @@ hipError_t launch_rstar_exch(const Dims &d, const Params &p, const Fields &f, co
   const int nbX = ((nHalo > 0 ? nHalo : 1) + 255) / 256;
   const unsigned nb = (unsigned)(nbR + nbX * nzMax * (x.n > 0 ? x.n : 1));
   hipLaunchKernelGGL(fuseEtaH ? k_rstar_exch<true> : k_rstar_exch<false>, dim3(nb), dim3(256), 0, s, d, p, f, srcOf, nbR, x,
-                     map, nHalo, ctr, nbX, nzMax, fromX);
+                     map, nHalo, ctr, nbX, nzMax, fromX, fuseEtaH ? empNext : 0);
   return hipGetLastError();
 }
 
@@ -251,19 +264,28 @@ hipError_t launch_rstar_exmix(const Dims &d, const Params &p, const Fields &f, c
 
 // opEarly: the operator and preconditioner were built beside DYNAMICS (launch_dyn_thermo);
 // pcHere (with opEarly): only the operator was, the preconditioner rides in this launch
+// iterPtr non-null: the next step's DO_OCEANIC_PHYS rides at the head of the grid
 hipError_t launch_update_r_star_cg2d(const Dims &d, const Params &p, const Fields &f, const long *srcOf, hipStream_t s,
-                                     bool sfp, bool opEarly, bool pcHere) {
+                                     bool sfp, bool opEarly, bool pcHere, const int *iterPtr) {
   const long n = d.n2 * d.nTiles;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const long ncol = (long)d.nx * d.ny * d.nT;
   const int nArr = sfp ? 6 : 2;
   const int nc = mg_colf_nc(ncol, d.Nr, nArr);
-  MG_ALLOW_LDS(k_update_r_star_cg2d_a<false>);
-  MG_ALLOW_LDS(k_update_r_star_cg2d_a<true>);
+  auto kPlain = k_update_r_star_cg2d_a<false, false>, kSfp = k_update_r_star_cg2d_a<true, false>,
+       kSfpPhys = k_update_r_star_cg2d_a<true, true>;
+  MG_ALLOW_LDS(kPlain);
+  MG_ALLOW_LDS(kSfp);
   const int nbPc = (opEarly && pcHere && p.nonlinFreeSurf > 2) ? (int)nb : 0;
-  hipLaunchKernelGGL(sfp ? k_update_r_star_cg2d_a<true> : k_update_r_star_cg2d_a<false>,
-                     dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbPc), dim3(256), mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc,
-                     opEarly ? 0 : 1, srcOf, nbPc);
+  if (iterPtr) {
+    if (!sfp) return hipErrorInvalidValue;   // (one_step pipelines only the fused right-hand side's layout)
+    MG_ALLOW_LDS(kSfpPhys);
+    const int nbPh = phys_hoist_blocks(d);
+    hipLaunchKernelGGL(kSfpPhys, dim3(mg_colf_blocks(ncol, nc) + (unsigned)(nbPc + nbPh)), dim3(256),
+                       mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc, opEarly ? 0 : 1, srcOf, nbPc, iterPtr, nbPh);
+  } else
+    hipLaunchKernelGGL(sfp ? kSfp : kPlain, dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbPc), dim3(256),
+                       mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc, opEarly ? 0 : 1, srcOf, nbPc, (const int *)nullptr, 0);
   if (p.nonlinFreeSurf > 2 && !opEarly) hipLaunchKernelGGL(k_update_cg2d_p, dim3(nb), dim3(256), 0, s, d, p, f, srcOf);
   return hipGetLastError();
 }

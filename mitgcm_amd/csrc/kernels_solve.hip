@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "cg2d.h"
+#include "gm_tensor.h"
 
 namespace mgcm {
 
@@ -1087,10 +1088,19 @@ __global__ void __launch_bounds__(256) k_exch_etaH(Dims d, Params p, Fields f, c
 // exchange source of each point -- exactly the etaN that SOLVE_FOR_PRESSURE's EXCH_XY_RL +
 // etaN = recip_Bo*cg2d_x (k_exch_eta) stores -- so k_exch_eta runs beside this kernel instead
 // of before it (it writes only etaN and cg2d_x's halo, which this kernel then does not read).
+// GM (MG_FUSE_PIPE): the next step's GMREDI_CALC_TENSOR on the first nbGm logical blocks
+// (gm_tensor.h; it reads the rhoInSitu and sigmaR that step's DO_OCEANIC_PHYS left earlier in
+// this step, and writes the tensor, which nothing else in this step reads any more)
+template <bool GM>
 __global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, int atInit, int nc,
-                                                   const long *__restrict__ etaSrc) {
+                                                   const long *__restrict__ etaSrc, int nbGm) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  MG_COLF(1, d.sNx, 1, d.sNy, nc)
+  int lb = mg_xcd_block();
+  if constexpr (GM) {
+    if (lb < nbGm) { gm_tensor_body(d, p, f, lb); return; }
+    lb -= nbGm;
+  }
+  MG_COLF_LB(1, d.sNx, 1, d.sNy, nc, lb)
   const int NS = d.Nr * NC_;
   // sH0 (r* only) last: launch_corr_cont allocates it only under r*
   double *sDiv = lds, *sMask = lds + NS, *sU = lds + 2 * NS, *sV = lds + 3 * NS, *sH0 = lds + 4 * NS;
@@ -1493,8 +1503,9 @@ hipError_t launch_exch_eta(const Dims &d, const Params &p, const Fields &f, cons
   return hipGetLastError();
 }
 
+// gmNext: the next step's GMREDI_CALC_TENSOR rides at the head of the grid (the column frame only)
 hipError_t launch_corr_cont(const Dims &d, const Params &p, const Fields &f, int atInit, hipStream_t s,
-                            const long *etaSrc) {
+                            const long *etaSrc, bool gmNext) {
   const long ncol = (long)d.sNx * d.sNy * d.nT;
   const int nArr = (p.nonlinFreeSurf > 0 && p.select_rStar != 0) ? 5 : 4;   // sH0 under r* only
   // deep grids: 32 columns per workgroup (LLC-90: 123 us against 140 at 16,
@@ -1505,6 +1516,7 @@ hipError_t launch_corr_cont(const Dims &d, const Params &p, const Fields &f, int
   if (atInit == 0 && !(p.nonlinFreeSurf > 0 && p.select_rStar != 0) && d.Nr == 50) {
     // (levels one at a time: loading batches of 5 or 10 levels ahead measured slower, 103
     // against 87 us, profiles/r05/corr_sb/)
+    if (gmNext) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_corr_cont_march<50>, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, s, d, p, f, etaSrc);
     return hipGetLastError();
   }
@@ -1512,9 +1524,16 @@ hipError_t launch_corr_cont(const Dims &d, const Params &p, const Fields &f, int
   // (round 4: a two-column form with 16-byte loads was bit-identical but slower on LLC-90,
   // 151 against 137 us, profiles/r04/corr2/ -- the column frame is bound by its serial column
   // sums and LDS round trips, not by the width of its loads; removed in round 5)
-  MG_ALLOW_LDS(k_corr_cont);
-  hipLaunchKernelGGL(k_corr_cont, dim3(mg_colf_blocks(ncol, nc)), dim3(256), mg_colf_lds(d.Nr, nc, nArr), s, d, p, f,
-                     atInit, nc, etaSrc);
+  if (gmNext) {
+    const int nbGm = (int)mg_plane_blocks(d.nx - 2, d.ny - 2, d.nT * d.Nr);
+    MG_ALLOW_LDS(k_corr_cont<true>);
+    hipLaunchKernelGGL(k_corr_cont<true>, dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbGm), dim3(256),
+                       mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, atInit, nc, etaSrc, nbGm);
+    return hipGetLastError();
+  }
+  MG_ALLOW_LDS(k_corr_cont<false>);
+  hipLaunchKernelGGL(k_corr_cont<false>, dim3(mg_colf_blocks(ncol, nc)), dim3(256), mg_colf_lds(d.Nr, nc, nArr), s, d, p, f,
+                     atInit, nc, etaSrc, 0);
   return hipGetLastError();
 }
 

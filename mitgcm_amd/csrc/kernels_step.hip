@@ -109,8 +109,10 @@ __global__ void __launch_bounds__(256) k_dt_l1f(Dims d, Params p, Fields f, int 
 }
 // launch [UPDATE_CG2D operator (nbOp blocks, 0 = none) | GMREDI_CALC_TENSOR | CALC_PHI_HYD |
 // del2uv (nbDel blocks, 0 = none)]
-static void launch_l1(const Dims &d, const Params &p, const Fields &f, int nbDel, hipStream_t s, int nbOp = 0) {
-  const int nbGm = (int)mg_plane_blocks(d.nx - 2, d.ny - 2, d.nT * d.Nr);
+// gm = false: without the tensor's blocks (it ran in the previous step's grids, MG_FUSE_PIPE)
+static void launch_l1(const Dims &d, const Params &p, const Fields &f, int nbDel, hipStream_t s, int nbOp = 0,
+                      bool gm = true) {
+  const int nbGm = gm ? (int)mg_plane_blocks(d.nx - 2, d.ny - 2, d.nT * d.Nr) : 0;
   if (phi_flat_on(p)) {
     const bool rs = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
     const bool qh = p.quasiHydrostatic && (p.select3dCoriScheme >= 1 || p.useNHMTerms);
@@ -254,9 +256,10 @@ hipError_t launch_tracer_hpair(const Dims &d, const Params &p, const Fields &f, 
 // CALC_PHI_HYD + THERMODYNAMICS' tracers + DYNAMICS in three launches on one stream
 // (after DO_OCEANIC_PHYS; dyn_thermo_fusable must hold).  srcOf != nullptr (default layout,
 // nonlinFreeSurf > 2, every tile): UPDATE_CG2D in the first two grids as well (ucg2d.h), and
-// launch_update_r_star_cg2d then runs with opEarly
+// launch_update_r_star_cg2d then runs with opEarly.  gmHere = false (the default layout only):
+// GMREDI_CALC_TENSOR of this step ran in the previous step's grids
 hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, const TracerArgs &aT, const TracerArgs &aS,
-                             const int *iterPtr, hipStream_t s, const long *srcOf) {
+                             const int *iterPtr, hipStream_t s, const long *srcOf, bool gmHere) {
   const dim3 blk(256);
   // front: phi's column frame (launch_phi_hyd's columns and LDS), del2uv's and the tracers' planes
   int ncPhi, nArrPhi, nbPhi;
@@ -271,7 +274,7 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
     // operator's blocks best
     const int nbU = srcOf ? ucg2d_blocks(d) : 0;
     const int nbOp1 = 0, nbPc2 = 0, nbOp2 = nbU, nbPc3 = nbU;
-    launch_l1(d, p, f, nbDel, s, nbOp1);
+    launch_l1(d, p, f, nbDel, s, nbOp1, gmHere);
     const bool ff4 = mom_ff4_on(true);
     const int nbMom = ff4 ? mom_ff4_blocks(d) : 2 * (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
     auto l2 = ff4 ? k_dt_l2<true, true> : k_dt_l2<true, false>;
@@ -286,7 +289,7 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
                        aS, iterPtr, ncTr, nbCd, nbImp, srcOf, nbPc3, dt_long_first());
     return hipGetLastError();
   }
-  if (srcOf) return hipErrorInvalidValue;   // (the operator rides only in the default layout)
+  if (srcOf || !gmHere) return hipErrorInvalidValue;   // (the operator rides, and the tensor leaves, only in the default layout)
   MG_ALLOW_LDS(k_dt_front<true>);
   hipLaunchKernelGGL(k_dt_front<true>, dim3((unsigned)(nbPhi + nbDel + 2 * nbTr)), blk,
                      mg_colf_lds(d.Nr, ncPhi, nArrPhi), s, d, p, f, aT, aS, iterPtr, ncPhi, nbPhi, nbDel, nbTr);

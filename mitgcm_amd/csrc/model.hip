@@ -73,15 +73,16 @@ hipError_t launch_exchange_uv_pairs(const Dims &, double *const *, double *const
                                    hipStream_t);
 hipError_t launch_exch_eta(const Dims &, const Params &, const Fields &, const long *, bool, int, hipStream_t,
                            int fromX = 0);
-hipError_t launch_corr_cont(const Dims &, const Params &, const Fields &, int, hipStream_t, const long *etaSrc = nullptr);
+hipError_t launch_corr_cont(const Dims &, const Params &, const Fields &, int, hipStream_t, const long *etaSrc = nullptr,
+                            bool gmNext = false);
 hipError_t launch_calc_r_star(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool fuseEtaH = false,
                               int fromX = 0);
 hipError_t launch_rstar_exmix(const Dims &, const Params &, const Fields &, const long *, bool, int, double *, double *, int,
                               const long *, int, int, const XFields &, const long *, int, hipStream_t);
 hipError_t launch_rstar_exch(const Dims &, const Params &, const Fields &, const long *, bool, const XFields &, const long *,
-                             int, int *, hipStream_t, int fromX = 0);
+                             int, int *, hipStream_t, int fromX = 0, int empNext = 0);
 hipError_t launch_update_r_star_cg2d(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool sfp = false,
-                                     bool opEarly = false, bool pcHere = false);
+                                     bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr);
 hipError_t launch_halo_pack(const Dims &, const XFields &, const long *, long, double *, int, hipStream_t);
 hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
                                bool *ringDone = nullptr);
@@ -89,7 +90,7 @@ hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, cons
                               bool impl = true);
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
 hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
-                             hipStream_t, const long *srcOf = nullptr);
+                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true);
 bool dyn_thermo_takes_gm(const Params &);
 hipError_t launch_gm_tensor(const Dims &, const Params &, const Fields &, hipStream_t);
 hipError_t launch_hfac_snapshot(const Dims &, const Fields &, double *, hipStream_t);
@@ -256,9 +257,11 @@ struct mgcm_model {
   long exchCap = 0;
   // hipGraphs of two FORWARD_STEPs, one per theta/salt ping-pong parity
   bool useGraph = true;
-  hipGraphExec_t graphExec[2][4] = {};   // [THERMODYNAMICS overlap off/on][tracer buffer parity]
-  hipGraphExec_t graph1Exec[2][4] = {};  // ONE step (callers that step one at a time: the Fortran drop-ins)
-  double *graph1Tr[2][4][4] = {};        // its tracer pointers after the step: theta, thetaNext, salt, saltNext
+  // [THERMODYNAMICS overlap off/on][tracer buffer parity][step modes: 0 plain, plain; 1 hoist, hoist; 2 hoist, last]
+  hipGraphExec_t graphExec[2][4][3] = {};
+  // ONE step (callers that step one at a time: the Fortran drop-ins) [..][..][step mode: 0 plain, 1 last]
+  hipGraphExec_t graph1Exec[2][4][2] = {};
+  double *graph1Tr[2][4][2][4] = {};     // its tracer pointers after the step: theta, thetaNext, salt, saltNext
   // overlap auto-selection (ovl_trial): both graphs timed on a copy of the state
   bool ovlAuto = false, ovlDecided = false;
   float ovlMs[2] = {0.f, 0.f};
@@ -1339,8 +1342,9 @@ static hipError_t calc_r_star(mgcm_model *m, bool fuseEtaH = false, int fromX = 
 }
 // sfp: k_sfp_rhs fused into the r* column pass (FORWARD_STEP on the whole domain only: in a
 // tile-sharded run the r* pass covers every tile and the right-hand side this process's own)
-static hipError_t update_r_star_cg2d(mgcm_model *m, bool sfp = false, bool opEarly = false, bool pcHere = false) {
-  return launch_update_r_star_cg2d(all_tiles(m->d), m->p, m->f, m->d_srcOf, m->stream, sfp, opEarly, pcHere);
+static hipError_t update_r_star_cg2d(mgcm_model *m, bool sfp = false, bool opEarly = false, bool pcHere = false,
+                                     const int *physNext = nullptr) {
+  return launch_update_r_star_cg2d(all_tiles(m->d), m->p, m->f, m->d_srcOf, m->stream, sfp, opEarly, pcHere, physNext);
 }
 
 int mgcm_init(mgcm_model *m) {
@@ -1779,7 +1783,44 @@ static XFields blocking_fields(const mgcm_model *m, int tracers) {
 // One FORWARD_STEP with the fused end-of-step kernels: EXCH(cg2d_x)+etaN,
 // correction+continuity, EXCH(eta)+UPDATE_ETAH, and every blocking exchange plus
 // the counter bump in one launch.  Same arithmetic as the separate C-ABI ops.
-static int one_step(mgcm_model *m) {
+//
+// The pipelined step (MG_FUSE_PIPE, step_pipelinable): DO_OCEANIC_PHYS and GMREDI_CALC_TENSOR
+// of a step read only the new theta and salt, totPhiHyd, the surface hFacC and EmPmR of the
+// step before it -- nothing its pressure solve, correction step, CALC_R_STAR or velocity
+// exchange produce -- so the step before runs them in two of its own grids, which are far from
+// full (phys.h oceanic_phys_point_t<true>: in UPDATE_R_STAR's grid; the tensor in the
+// correction step's), and the step itself starts at CALC_PHI_HYD: one launch fewer, and the
+// fold's first grid without the tensor's blocks.  mgcm_forward_step runs the two stand-alone
+// for the first step of a call (so a put between calls is honoured) and leaves the last step
+// without the riders, so after a call every field holds what the plain steps leave.
+enum StepMode {
+  STEP_PLAIN = 0,   // the step runs its own DO_OCEANIC_PHYS + tensor
+  STEP_HOIST = 1,   // its own are already done; it runs the next step's
+  STEP_LAST = 2     // its own are already done; it runs nobody's (the last step of a call)
+};
+// a call of fewer steps keeps the plain step: the stand-alone head of a pipelined call costs
+// two launches, each hoisting step saves one (profiles/r07/step_pipeline/threshold.md)
+#define MG_PIPE_MIN_STEPS 4
+// where the substitutions of the hoisted pass are exact (phys.h) and its host grids run
+static bool step_pipelinable(mgcm_model *m) {
+  const Params &p = m->p;
+  const bool tracers = p.tempStepping && p.saltStepping;
+  const bool stagger = p.staggerTimeStep != 0 && p.momStepping;
+  if (stagger || !m->overlap || !p.momStepping || !tracers || !mg_fuse_on(MG_FUSE_PIPE)) return false;
+  if (p.nonlinFreeSurf <= 0 || p.select_rStar <= 0 || !p.useRealFreshWaterFlux || !p.exactConserv) return false;
+  if (m->d.nT != m->d.nTiles || m->uvMap || !m->d_srcOf) return false;
+  if (p.nonlinFreeSurf > 0 && p.select_rStar > 0 && m->snapH && mg_fuse_on(MG_FUSE_TCG)) return false;
+  const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
+  if (!dyn_thermo_fusable(m->d, p, aT, aS) || !dyn_thermo_takes_gm(p) || phys_phi_fusable(m->d, p)) return false;
+  // the r* pass with the right-hand side and CALC_R_STAR + the exchanges: the grids that carry the riders
+  if (!mg_fuse_on(MG_FUSE_SFP) || !mg_hfuse(MG_FUSE_END, m->d.nx, m->d.ny, m->d.nT, m->d.Nr)) return false;
+  // (JMD95P reads totPhiHyd's halo: exact at the exchange source only where it is exchanged)
+  if (p.eosType == 1 && p.selectP_inEOS_Zc == 2 && !p.storePhiHyd4Phys) return false;
+  return true;
+}
+static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
+  const bool pipe = mode != STEP_PLAIN, hoist = mode == STEP_HOIST;
+  if (pipe && !step_pipelinable(m)) return set_err("one_step: the pipelined step does not apply to this model");
   // THERMODYNAMICS reads u, v, w, hFac and DO_OCEANIC_PHYS's outputs and writes only the
   // tracers' other buffers and AB histories; DYNAMICS reads none of those.  So once
   // DO_OCEANIC_PHYS is done the two run concurrently (second stream), joined before
@@ -1860,7 +1901,7 @@ static int one_step(mgcm_model *m) {
   const bool physPhi = !stagger && m->p.momStepping && phys_phi_fusable(m->d, m->p);
   // (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
   m->stepLayout = (dtFused ? 1 : 0) | (physPhi ? 2 : 0) | (forkable && !dtFused ? 4 : 0) |
-                  ((forkable && m->p.nonlinFreeSurf <= 0) || tcg ? 8 : 0);
+                  ((forkable && m->p.nonlinFreeSurf <= 0) || tcg ? 8 : 0) | (pipe ? 16 : 0);
   // GMREDI_CALC_TENSOR beside CALC_PHI_HYD (launch_gm_phi) where THERMODYNAMICS, its reader,
   // runs after DYNAMICS (staggered, or forked after CALC_DIV_GHAT) and the fold does not apply
   const bool gmPhi = (stagger || thermoLate) && !dtFused && !physPhi && !m->timing && gm_phi_fusable(m->d, m->p);
@@ -1869,6 +1910,7 @@ static int one_step(mgcm_model *m) {
   bool ringPhys = false;
   const bool ringPhysOk = !ringAside && !physPhi && mom_ring_separable(m->d, m->p) && mg_fuse_on(MG_FUSE_RINGP);
   auto phys = [&]() -> int {
+    if (pipe) return 0;   // (done in the previous step's grids, or by mgcm_forward_step's head)
     if (physPhi) TIMED(K_PHYS, launch_phys_phi(m->d, m->p, m->f, m->d_ctr, m->stream));
     // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
     else TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream,
@@ -1893,7 +1935,8 @@ static int one_step(mgcm_model *m) {
   // removed in round 5)
   if (m->p.momStepping) {
     if (dtFused) {
-      TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, aT, aS, m->d_ctr, m->stream, opEarly ? m->d_srcOf : nullptr));
+      TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, aT, aS, m->d_ctr, m->stream, opEarly ? m->d_srcOf : nullptr,
+                                     !pipe));
       std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new tracers are the other buffers
       std::swap(m->f.salt, m->f.saltNext);
     } else if (physPhi) TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, !ringAside && !ringPhys));
@@ -1910,7 +1953,7 @@ static int one_step(mgcm_model *m) {
     // walking every 2-D point costs more than the launch it saves)
     const bool sfpFused = mg_fuse_on(MG_FUSE_SFP) && m->p.nonlinFreeSurf > 0 && m->d.nT == m->d.nTiles;
     if (m->p.nonlinFreeSurf > 0)
-      TIMED(K_RSTAR, update_r_star_cg2d(m, sfpFused, opEarly, false));
+      TIMED(K_RSTAR, update_r_star_cg2d(m, sfpFused, opEarly, false, hoist ? m->d_ctr : nullptr));
     if (!sfpFused) TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
     // the late fork: THERMODYNAMICS beside the CG2D only, CALC_DIV_GHAT (an HBM stream, on the
     // critical path) alone before it -- LLC-90 1.528-1.532 -> 1.474-1.476 ms/step, alternating
@@ -1942,7 +1985,7 @@ static int one_step(mgcm_model *m) {
       TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, false, 0, m->stream));
     }
     if (lateJoin || tcgFork) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
-    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, (etaAside || etaX) ? m->d_srcOf : nullptr));
+    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, (etaAside || etaX) ? m->d_srcOf : nullptr, hoist));
     if (etaAside) HIPCHK(hipStreamWaitEvent(m->stream, m->evEta1, 0));
     // forward_step.F:965-977: CALC_R_STAR(etaH(n+1)); the next step's RESET_NLFS_VARS +
     // UPDATE_R_STAR(.FALSE.) restore the hFac in place, so they are not repeated here.
@@ -1957,7 +2000,8 @@ static int one_step(mgcm_model *m) {
                mg_hfuse(MG_FUSE_END, m->d.nx, m->d.ny, m->d.nT, m->d.Nr);
     if (endFused)
       TIMED(K_RSTAR, launch_rstar_exch(m->d, m->p, m->f, m->d_srcOf, fuseEtaH, blocking_fields(m), m->d_halo, m->nHalo,
-                                       m->d_ctr, m->stream, etaX ? 1 : 0));
+                                       m->d_ctr, m->stream, etaX ? 1 : 0,
+                                       hoist && m->p.periodicExternalForcing ? 1 : 0));
     else if (m->p.nonlinFreeSurf > 0) {
       stagEx = stagger && tracers && m->uvMap && m->d.nT == m->d.nTiles &&
                mg_hfuse(MG_FUSE_ENDS, m->d.nx, m->d.ny, m->d.nT, m->d.Nr);
@@ -1992,11 +2036,13 @@ static int one_step(mgcm_model *m) {
 
 static void drop_graphs(mgcm_model *m) {
   for (auto &row : m->graphExec)
-    for (auto &ge : row)
-      if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+    for (auto &col : row)
+      for (auto &ge : col)
+        if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
   for (auto &row : m->graph1Exec)
-    for (auto &ge : row)
-      if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+    for (auto &col : row)
+      for (auto &ge : col)
+        if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
 }
 
 // Which theta/salt ping-pong buffers are current (the kernels' arguments differ).
@@ -2007,47 +2053,50 @@ static int buffer_parity(const mgcm_model *m) {
 // Two FORWARD_STEPs captured once into a hipGraph per buffer parity (the tracer
 // ping-pong swaps twice, so the pointers are back where they started), then
 // replayed: no per-kernel host launch cost inside a batch.
-static int two_step_graph(mgcm_model *m, hipGraphExec_t *out) {
+// v: 0 two plain steps; 1 two pipelined steps that both hoist; 2 a hoisting step and the last
+// step of a call (StepMode)
+static int two_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
   const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
-  if (!m->graphExec[o][q]) {
+  if (!m->graphExec[o][q][v]) {
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    int rc = one_step(m);
-    if (!rc) rc = one_step(m);
+    int rc = one_step(m, v ? STEP_HOIST : STEP_PLAIN);
+    if (!rc) rc = one_step(m, v == 1 ? STEP_HOIST : v == 2 ? STEP_LAST : STEP_PLAIN);
     hipError_t e = hipStreamEndCapture(m->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return -1; }
     HIPCHK(e);
-    e = hipGraphInstantiate(&m->graphExec[o][q], g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(&m->graphExec[o][q][v], g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     HIPCHK(e);
   }
-  *out = m->graphExec[o][q];
+  *out = m->graphExec[o][q][v];
   return 0;
 }
 
 // One FORWARD_STEP captured per buffer parity (the tracer ping-pong flips it, so consecutive
 // single steps alternate between two of these graphs): a caller that steps one at a time --
 // the Fortran drop-ins, with host work between steps -- still replays instead of launching.
-static int one_step_graph(mgcm_model *m, hipGraphExec_t *out) {
+// v: 0 a plain step; 1 the last step of a pipelined call
+static int one_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
   const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
-  if (!m->graph1Exec[o][q]) {
+  if (!m->graph1Exec[o][q][v]) {
     double *pre[4] = {m->f.theta, m->f.thetaNext, m->f.salt, m->f.saltNext};
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = one_step(m);
+    const int rc = one_step(m, v ? STEP_LAST : STEP_PLAIN);
     hipError_t e = hipStreamEndCapture(m->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return -1; }
     HIPCHK(e);
-    e = hipGraphInstantiate(&m->graph1Exec[o][q], g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(&m->graph1Exec[o][q][v], g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     HIPCHK(e);
     // the capture ran one_step's host side (CYCLE_TRACER's pointer swaps) without launching:
     // keep the pointers it leaves for every replay, and undo them until the replay
     double **tr[4] = {&m->f.theta, &m->f.thetaNext, &m->f.salt, &m->f.saltNext};
-    for (int k = 0; k < 4; k++) m->graph1Tr[o][q][k] = *tr[k];
+    for (int k = 0; k < 4; k++) m->graph1Tr[o][q][v][k] = *tr[k];
     m->f.theta = pre[0]; m->f.thetaNext = pre[1]; m->f.salt = pre[2]; m->f.saltNext = pre[3];
   }
-  *out = m->graph1Exec[o][q];
+  *out = m->graph1Exec[o][q][v];
   return 0;
 }
 int mgcm_tracer_parity(mgcm_model *m, int set) {
@@ -2063,9 +2112,9 @@ int mgcm_tracer_parity(mgcm_model *m, int set) {
 }
 
 // after a one-step replay: the tracer pointers one_step would have left
-static void one_step_graph_done(mgcm_model *m, int o, int q) {
-  m->f.theta = m->graph1Tr[o][q][0]; m->f.thetaNext = m->graph1Tr[o][q][1];
-  m->f.salt = m->graph1Tr[o][q][2]; m->f.saltNext = m->graph1Tr[o][q][3];
+static void one_step_graph_done(mgcm_model *m, int o, int q, int v) {
+  m->f.theta = m->graph1Tr[o][q][v][0]; m->f.thetaNext = m->graph1Tr[o][q][v][1];
+  m->f.salt = m->graph1Tr[o][q][v][2]; m->f.saltNext = m->graph1Tr[o][q][v][3];
 }
 
 static int ovl_trial(mgcm_model *m);
@@ -2079,6 +2128,7 @@ int mgcm_prepare(mgcm_model *m) {
   HIPCHK(hipSetDevice(m->device));
   if (m->ovlAuto && !m->ovlDecided && ovl_trial(m)) return -1;
   hipGraphExec_t ge;
+  if (step_pipelinable(m) && (two_step_graph(m, &ge, 1) || two_step_graph(m, &ge, 2))) return -1;
   return two_step_graph(m, &ge);
 }
 
@@ -2152,11 +2202,16 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipMemsetAsync(m->d_ctr + 1, 0, sizeof(int), m->stream));
   int s = 0;
+  if (m->useGraph && !m->timing && m->ovlAuto && !m->ovlDecided && nsteps >= 2 && ovl_trial(m)) return -1;
+  // the pipelined call (one_step's StepMode): DO_OCEANIC_PHYS + GMREDI_CALC_TENSOR of the first
+  // step stand-alone, from the fields as the caller left them; every step but the last then
+  // runs the next step's, and the last leaves every field as the plain step does
+  const bool pipe = nsteps >= MG_PIPE_MIN_STEPS && step_pipelinable(m);
+  if (pipe) TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream));
   if (m->useGraph && !m->timing) {
-    if (m->ovlAuto && !m->ovlDecided && nsteps >= 2 && ovl_trial(m)) return -1;
     for (; s + 2 <= nsteps; s += 2) {
       hipGraphExec_t ge;
-      if (two_step_graph(m, &ge)) return -1;
+      if (two_step_graph(m, &ge, pipe ? (s + 2 == nsteps ? 2 : 1) : 0)) return -1;
       HIPCHK(hipGraphLaunch(ge, m->stream));
     }
   }
@@ -2164,13 +2219,14 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
   if (s < nsteps && m->useGraph && !m->timing) {
     const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
     hipGraphExec_t ge;
-    if (one_step_graph(m, &ge)) return -1;
+    if (one_step_graph(m, &ge, pipe ? 1 : 0)) return -1;
     HIPCHK(hipGraphLaunch(ge, m->stream));
-    one_step_graph_done(m, o, q);
+    one_step_graph_done(m, o, q, pipe ? 1 : 0);
     s++;
   }
   for (; s < nsteps; s++)
-    if (one_step(m)) return -1;
+    if (one_step(m, pipe ? (s == nsteps - 1 ? STEP_LAST : STEP_HOIST) : STEP_PLAIN)) return -1;
+  m->stepLayout = (m->stepLayout & ~16) | (pipe ? 16 : 0);   // (the layout this call ran, whichever graph was built last)
   m->lastBatch = nsteps;
   return 0;
 }

@@ -1,6 +1,7 @@
 // phys.h -- DO_OCEANIC_PHYS's per-point work (EOS, surface forcing, IVDC), shared by
-// k_oceanic_phys (kernels_thermo.hip) and the fused DO_OCEANIC_PHYS + CALC_PHI_HYD column
-// pass k_phys_phi (kernels_dyn.hip).
+// k_oceanic_phys (kernels_thermo.hip), the fused DO_OCEANIC_PHYS + CALC_PHI_HYD column
+// pass k_phys_phi (kernels_dyn.hip) and the next step's pass in UPDATE_R_STAR's grid
+// (kernels_rstar.hip, MG_FUSE_PIPE).
 #pragma once
 #include "common.h"
 
@@ -59,17 +60,42 @@ __device__ __forceinline__ double find_rho(const Params &p, const Fields &f, int
 // One point (i,j,k) of the full halo range: FREEZE_SURFACE only changes theta(k=1), so
 // every reader of theta(k=1) applies the clamp itself and the k = 1 thread stores it.
 // Returns rhoInSitu(i,j,k) (also stored).
-__device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
-                                                     int i, int j, int k, int t) {
+//
+// HOIST: the pass of the NEXT step, run inside this step once its new theta and salt are
+// written (MG_FUSE_PIPE; it rides in UPDATE_R_STAR's grid, before the pressure solve, the
+// correction step, CALC_R_STAR, the blocking exchanges and the counter bump).  The same
+// expression trees on the values the next step's own pass would read:
+//   - the time is that of iteration myIter + 1;
+//   - theta, salt and totPhiHyd of a halo point are read at the point's exchange source
+//     (srcOf >= 0, else the point itself): what the end-of-step exchange stores there;
+//   - hFacC(k=1) is h0FacC*rStarFacC, the expression UPDATE_R_STAR is storing in this grid;
+//   - PmEpR is -EmPmR of this step, what CALC_R_STAR's pass stores at the end of it;
+//   - the new EmPmR goes to EmPmRnext (this step's correction step and CALC_R_STAR still read
+//     EmPmR; CALC_R_STAR's pass moves it over, calc_r_star_body), every other output in place:
+//     nothing later in this step reads them;
+//   - FREEZE_SURFACE's clamp is stored at points that are their own source only: the exchange
+//     then copies the clamped value into the images, as it finds them after today's pass.  (A
+//     thread of an image may read its source before or after the owner's store; both clamp to
+//     the same value.)
+template <bool HOIST>
+__device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
+                                                       const long *__restrict__ srcOf, int i, int j, int k, int t) {
   const long q = MG_I2(d, i, j, t), q31 = MG_I3(d, i, j, 1, t);
+  // the 3-D offset, at level 1, of the point theta / salt / totPhiHyd are read at
+  long r31 = q31;
+  bool own = true;
+  if constexpr (HOIST) {
+    const long sq = srcOf[q];
+    if (sq >= 0) { r31 = (sq / d.n2) * d.n3 + sq % d.n2; own = false; }
+  }
   auto theta_at = [&](int kk) {
-    const double v = f.theta[MG_I3(d, i, j, kk, t)];
+    const double v = f.theta[HOIST ? r31 + (long)(kk - 1) * d.n2 : MG_I3(d, i, j, kk, t)];
     return (kk == 1 && p.allowFreezing && v < -1.9) ? -1.9 : v;
   };
   if (k == 1 && p.periodicExternalForcing) {
     const long N2 = d.n2 * d.nTiles;
     const double cycleLength = p.externForcingCycle, recSpacing = p.externForcingPeriod;
-    const double currentTime = (double)(*iterPtr) * p.deltaTClock;
+    const double currentTime = (double)(*iterPtr + (HOIST ? 1 : 0)) * p.deltaTClock;
     const int nbRec = (int)llround(cycleLength / recSpacing);
     const double locTime = currentTime - recSpacing * 0.5 + cycleLength * (double)(2 - llround(currentTime / cycleLength));
     const double tmpTime = fmod(locTime, cycleLength);
@@ -77,7 +103,7 @@ __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params
     const int tRec2 = 1 + tRec1 % nbRec;
     const double aW = (tmpTime - recSpacing * (double)(tRec1 - 1)) / recSpacing;
     const double bW = 1.0 - aW;
-    double *dst[6] = {f.SST, f.SSS, f.fu, f.fv, f.Qnet, f.EmPmR};
+    double *dst[6] = {f.SST, f.SSS, f.fu, f.fv, f.Qnet, HOIST ? f.EmPmRnext : f.EmPmR};
 #pragma unroll
     for (int v = 0; v < 6; v++) {
       const double *r = f.forcRec + (long)v * p.nForcRec * N2;
@@ -85,18 +111,20 @@ __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params
     }
   }
   if (k == 1) {
-    const double th1 = theta_at(1), s1 = f.salt[q31];
-    if (p.allowFreezing) f.theta[q31] = th1;
+    const double th1 = theta_at(1), s1 = f.salt[HOIST ? r31 : q31];
+    if (p.allowFreezing && own) f.theta[q31] = th1;
     const double mass2rUnit = 1.0 / p.rhoConst, recip_Cp = 1.0 / p.HeatCapacity_Cp;
-    double sfT = -(f.lambdaThetaClimRelax[q] * (th1 - f.SST[q]) * f.drF[0] * f.hFacC[q31]);
-    double sfS = -(f.lambdaSaltClimRelax[q] * (s1 - f.SSS[q]) * f.drF[0] * f.hFacC[q31]);
+    const double hFac1 = HOIST ? f.h0FacC[q31] * f.rStarFacC[q] : f.hFacC[q31];
+    double sfT = -(f.lambdaThetaClimRelax[q] * (th1 - f.SST[q]) * f.drF[0] * hFac1);
+    double sfS = -(f.lambdaSaltClimRelax[q] * (s1 - f.SSS[q]) * f.drF[0] * hFac1);
     sfT = sfT - f.Qnet[q] * recip_Cp * mass2rUnit;
     sfS = sfS - 0.0 * mass2rUnit;   // saltFlux = 0
     const double UNSET_RL = 123456.7;
     if (p.nonlinFreeSurf > 0 && p.useRealFreshWaterFlux) {
       // external_forcing_surf.F:253-277: PmEpR changes the column height
-      if (p.temp_EvPrRn != UNSET_RL) sfT = sfT + f.PmEpR[q] * (p.temp_EvPrRn - th1) * mass2rUnit;
-      if (p.salt_EvPrRn != UNSET_RL) sfS = sfS + f.PmEpR[q] * (p.salt_EvPrRn - s1) * mass2rUnit;
+      const double pmepr = HOIST ? -f.EmPmR[q] : f.PmEpR[q];
+      if (p.temp_EvPrRn != UNSET_RL) sfT = sfT + pmepr * (p.temp_EvPrRn - th1) * mass2rUnit;
+      if (p.salt_EvPrRn != UNSET_RL) sfS = sfS + pmepr * (p.salt_EvPrRn - s1) * mass2rUnit;
     } else if (p.convertFW2Salt == -1.0) {
       if (p.temp_EvPrRn != UNSET_RL) sfT = sfT + f.EmPmR[q] * (th1 - p.temp_EvPrRn) * mass2rUnit;
       if (p.salt_EvPrRn != UNSET_RL) sfS = sfS + f.EmPmR[q] * (s1 - p.salt_EvPrRn) * mass2rUnit;
@@ -108,13 +136,14 @@ __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params
     f.surfaceForcingS[q] = sfS;
   }
   const long q3 = MG_I3(d, i, j, k, t);
-  const double rho = find_rho(p, f, k, q3, theta_at(k), f.salt[q3]);
+  const long r3 = HOIST ? r31 + (long)(k - 1) * d.n2 : q3;   // where theta, salt and totPhiHyd are read
+  const double rho = find_rho(p, f, k, r3, theta_at(k), f.salt[r3]);
   f.rhoInSitu[q3] = rho;
   const bool calcConvect = p.ivdc_kappa != 0.0;
   double conv = 0.0, sigmaR = 0.0;
   if (k >= 2 && (calcConvect || p.useGMRedi)) {
     const long q3u = MG_I3(d, i, j, k - 1, t);
-    const double rhoKm1 = find_rho(p, f, k, q3, theta_at(k - 1), f.salt[q3u]);
+    const double rhoKm1 = find_rho(p, f, k, r3, theta_at(k - 1), f.salt[r3 - d.n2]);
     sigmaR = f.maskC[q3] * f.maskC[q3u] * f.recip_drC[k - 1] * p.rkSign * (rho - rhoKm1);
     if (calcConvect) conv = (-sigmaR * p.gravitySign > 0.0) ? 1.0 : 0.0;
   }
@@ -122,6 +151,19 @@ __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params
   if (p.useGMRedi) f.sigmaR[q3] = sigmaR;
   return rho;
 }
+__device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
+                                                     int i, int j, int k, int t) {
+  return oceanic_phys_point_t<false>(d, p, f, iterPtr, nullptr, i, j, k, t);
+}
+// the next step's pass on the logical blocks of another kernel's grid: k_oceanic_phys's frame
+// (one thread per (i,j,k) of the full halo range, phys_hoist_blocks blocks)
+__device__ __forceinline__ void phys_hoist_body(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
+                                                const long *__restrict__ srcOf, int lb) {
+  MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  oceanic_phys_point_t<true>(d, p, f, iterPtr, srcOf, i, j, k, t);
+}
+inline int phys_hoist_blocks(const Dims &d) { return (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr); }
 
 
 }  // namespace mgcm

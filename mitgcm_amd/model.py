@@ -212,10 +212,12 @@ class Model:
 
     def step_layout(self):
         """The launch layout of the last step built (mgcm_get_param 'stepLayout'): which
-        fusions of one_step (model.hip) the timed graph and the eager timed pass run."""
+        fusions of one_step (model.hip) the timed graph and the eager timed pass run.
+        'pipelined': the last forward_step call ran the next step's DO_OCEANIC_PHYS and
+        GMREDI_CALC_TENSOR inside each step (MGCM_STEP_FUSE bit 16384; calls of 4 steps or more)."""
         b = int(lib().mgcm_get_param(self.h, b"stepLayout"))
         return {"dyn_thermo_fused": bool(b & 1), "phys_phi_fused": bool(b & 2), "thermo_second_stream": bool(b & 4),
-                "late_join": bool(b & 8)}
+                "late_join": bool(b & 8), "pipelined": bool(b & 16)}
 
     def cg2d_fma(self):
         """True when the selected CG2D kernel solves in fused multiply-adds (cg2dUseFMA): the
