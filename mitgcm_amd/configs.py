@@ -422,9 +422,10 @@ def solid_body_cs32(data_dir=None):
     return g, params, state
 
 
-def advect_cs(data_dir=None, grid_dir=None):
+def advect_cs(sNx=32, sNy=32, data_dir=None, grid_dir=None):
     """verification/advect_cs: cubed sphere, 6 faces of 32x32 (pkg/exch2, code/SIZE.h
-    sNx=sNy=32, OL=4, one tile per face), 1 level (delR=1e5, Ro_SeaLevel=1e5: no bathymetry),
+    sNx=sNy=32, OL=4, one tile per face; other sNx, sNy divide every face into tiles of
+    sNx x sNy), 1 level (delR=1e5, Ro_SeaLevel=1e5: no bathymetry),
     momStepping=F: the solid-body rotation of code/ini_vel.F (psi = fac*fCoriG with
     omegaprime = 38.60328935834681/rSphere) advects theta from T.init with the DST3
     flux-limited multi-dimensional scheme (tempAdvScheme=33: the cube's 3-pass split,
@@ -436,8 +437,8 @@ def advect_cs(data_dir=None, grid_dir=None):
     d = data_dir or os.path.join(GOLDEN, "advect_cs")
     gd = grid_dir or os.path.join(GOLDEN, "global_ocean.cs32x15")
     n = 32
-    topo = cube_topology(n, 32, 32, 4)
-    g = Grid(32, 32, 4, 4, 1, nSx=6, nSy=1, topology=topo)
+    topo = cube_topology(n, sNx, sNy, 4)
+    g = Grid(sNx, sNy, 4, 4, 1, nSx=topo.nTiles, nSy=1, topology=topo)
     g.usingCurvilinearGrid = True
     g.ini_vertical_grid([1.0e5], Ro_SeaLevel=1.0e5)
     recs = [np.fromfile(os.path.join(gd, "grid_cs32.face%03d.bin" % f), dtype=">f8").astype(np.float64)
@@ -482,10 +483,11 @@ CS32_FORCING = {"taux": "trenberth_taux.bin", "tauy": "trenberth_tauy.bin", "Qne
                 "EmPmR": "shiEmPR_cs32.bin", "SST": "lev_surfT_cs_12m.bin", "SSS": "lev_surfS_cs_12m.bin"}
 
 
-def global_ocean_cs32x15(data_dir=None, sNy=32, params_over=None):
+def global_ocean_cs32x15(sNx=32, sNy=32, data_dir=None, params_over=None):
     """verification/global_ocean.cs32x15 (BASELINE config 3): 6 faces of 32x32 on pkg/exch2,
     one 32x32 tile per face at OL=4 (SURVEY 8(d) C3 layout; sNy=16 gives the reference's
-    code/SIZE.h tiling sNx=32, sNy=16, nSx=12, two tiles per face), 15 levels,
+    code/SIZE.h tiling sNx=32, sNy=16, nSx=12, two tiles per face; any sNx, sNy that divide
+    32 re-tile the faces), 15 levels,
     curvilinear grid from grid_cs32.faceNNN.bin (18 records incl. AngleCS/SN,
     radius_fromHorizGrid=6370e3), bathy_Hmin50.bin.  input/data: viscAh=3e5, viscAr=1e-3,
     diffKrT=diffKrS=3e-5, ivdc_kappa=10, implicitDiffusion, JMD95Z, staggerTimeStep,
@@ -500,8 +502,8 @@ def global_ocean_cs32x15(data_dir=None, sNy=32, params_over=None):
     pickup.0000072000, which the reference tree does not hold)."""
     d = data_dir or os.path.join(GOLDEN, "global_ocean.cs32x15")
     n, Nr = 32, 15
-    topo = cube_topology(n, 32, sNy, 4)
-    g = Grid(32, sNy, 4, 4, Nr, nSx=topo.nTiles, nSy=1, topology=topo)
+    topo = cube_topology(n, sNx, sNy, 4)
+    g = Grid(sNx, sNy, 4, 4, Nr, nSx=topo.nTiles, nSy=1, topology=topo)
     g.usingCurvilinearGrid = True
     g.ini_vertical_grid(LATLON_DELR)
     recs = [np.fromfile(os.path.join(d, "grid_cs32.face%03d.bin" % f), dtype=">f8").astype(np.float64)
@@ -653,4 +655,119 @@ def llc_synthetic(n=90, Nr=50, OL=4, tile=None, seed=20261015):
                   diffKhT=0.0, diffKrT=1.0e-5, diffKhS=0.0, diffKrS=1.0e-5, ivdc_kappa=10.0, implicitDiffusion=1,
                   usingCurvilinearGrid=1, rSphere=6370.0e3, integr_GeoPot=2, eosType=0, tAlpha=2.0e-4, sBeta=7.4e-4)
     state = {"theta": theta, "salt": salt, "tRef": tRef, "sRef": np.full(Nr, 35.0), "fu": fu[:, 0], "fv": fv[:, 0]}
+    return g, params, state
+
+
+def _facets_to_tiles(g, fld):
+    """Facet fields fld[f] of shape (..., n, n) -> tile layout (nTiles, ..., ny, nx), interiors
+    only (halos 0): tile t holds rows tBy+1..tBy+sNy, columns tBx+1..tBx+sNx of its facet."""
+    topo = g.topo
+    lead = np.shape(fld[0])[:-2]
+    out = np.zeros((g.nTiles,) + lead + (g.ny, g.nx))
+    inner = g.sl(1, g.sNx, 1, g.sNy)
+    for t in range(g.nTiles):
+        tid = t + 1
+        y0, x0 = topo.tBy[tid], topo.tBx[tid]
+        out[(t, Ellipsis) + inner] = fld[topo.face[tid] - 1][..., y0:y0 + g.sNy, x0:x0 + g.sNx]
+    return out
+
+
+def cube_synthetic(n, Nr, sNx=None, sNy=None, OL=4, seed=20261020, params_over=None):
+    """A synthetic ocean on the 6-facet cube topology (cube_topology), made to tell indices,
+    metrics and edge rotations apart: six facets of n x n cells in tiles of sNx x sNy (default
+    n: one tile per facet), Nr levels (llc_delr), OL halo rows.  Every random or seeded field
+    is drawn on the facets' global index space, (6, [Nr,] n, n), and cut into tiles afterwards:
+    one seed is one ocean at every tiling.
+      metrics    no sphere behind them: per facet and per array a smooth seeded modulation
+                 1 + 0.25 sin(2 pi (a i / n + p)) cos(2 pi (b j / n + q)) of dx ~ 1e5 m and of
+                 dy ~ 0.7e5 m (anisotropic, non-uniform, different on every facet), the
+                 F / C / G / V / U variants of each spacing a further +-3 % apart and the four
+                 areas rA, rAz, rAw, rAs +-3 % from dxF dyF and from one another; the halos
+                 come from the exchanges of INI_CURVILINEAR_GRID, so across a rotated edge a
+                 dx halo holds the neighbour's dy;
+      Coriolis   f = 2 Omega sin(lat) of a smooth seeded per-facet 'latitude' in +-60 degrees,
+                 drawn apart at cell centres (fCori) and corners (fCoriG);
+      bathymetry depths uniform in 500..4000 m, about 15 % land, independent from cell to cell:
+                 islands and partial cells next to tile corners and facet corners.  A column
+                 shallower than 4000 m (sum of delR) scales the depths by sum(delR) / 4000, so
+                 that the bottom still varies on a few-level grid;
+      state      T = tRef(k) + 0.01 N(0,1), S = 35 + 0.001 N(0,1); u, v = 0.1 N(0,1) m/s,
+                 exchanged with signs and masked: the advective and vorticity terms are of
+                 full size from the first step; eta = 0;
+      forcing    wind stress fu, fv = 0.1 N(0,1) N/m2, exchanged with signs;
+      physics    llc_synthetic's, then params_over (r*: nonlinFreeSurf = 4, select_rStar = 2
+                 adds the h0Fac / rLow / rSurf state of the other r* configurations).
+    Returns (grid, params, state)."""
+    from math import pi
+    sNx, sNy = sNx or n, sNy or n
+    topo = cube_topology(n, sNx, sNy, OL)
+    g = Grid(sNx, sNy, OL, OL, Nr, nSx=topo.nTiles, nSy=1, topology=topo)
+    g.usingCurvilinearGrid = True
+    delR = llc_delr(Nr)
+    g.ini_vertical_grid(delR)
+    rng = np.random.default_rng(seed)
+    jj, ii = np.meshgrid(np.arange(n + 1, dtype=np.float64), np.arange(n + 1, dtype=np.float64), indexing="ij")
+
+    def smooth():
+        a, b = rng.integers(1, 3, 2)
+        p, q = rng.random(2)
+        return np.sin(2.0 * pi * (a * ii / n + p)) * np.cos(2.0 * pi * (b * jj / n + q))
+    recs = []
+    for _ in range(6):
+        r = np.zeros((18, n + 1, n + 1))
+        dx = 1.0e5 * (1.0 + 0.25 * smooth())
+        dy = 0.7e5 * (1.0 + 0.25 * smooth())
+        r[0], r[1] = 180.0 * smooth(), 60.0 * smooth()           # XC, YC (degrees)
+        r[5], r[6] = 180.0 * smooth(), 60.0 * smooth()           # XG, YG
+        for q in (2, 7, 10, 14):                                 # DXF DXV DXC DXG
+            r[q] = dx * (1.0 + 0.03 * smooth())
+        for q in (3, 8, 11, 15):                                 # DYF DYU DYC DYG
+            r[q] = dy * (1.0 + 0.03 * smooth())
+        for q in (4, 9, 12, 13):                                 # RA RAZ RAW RAS
+            r[q] = r[2] * r[3] * (1.0 + 0.03 * smooth())
+        r[16], r[17] = 1.0, 0.0                                  # AngleCS, AngleSN
+        recs.append(r)
+    g.ini_curvilinear_grid(recs, radius_fromHorizGrid=6370.0e3, rSphere=6370.0e3, anglesFromFile=True)
+    g.ini_cori(selectCoriMap=2)
+    g.f["fCoriCos"] = g.z2()
+    depth = (500.0 + 3500.0 * rng.random((6, n, n))) * min(1.0, sum(delR) / 4000.0)
+    depth[rng.random((6, n, n)) < 0.15] = 0.0
+    g.ini_depths_masks(_facets_to_tiles(g, -depth), hFacMin=0.1, hFacMinDr=20.0, gBaro=9.81)
+    dt = 3600.0
+    g.ini_cg2d(dt, dt, 1e-9)
+    rC = g.f["rC"][:Nr]
+    tRef = 2.0 + 18.0 * np.exp(rC / 1000.0)
+    mC = g.f["maskC"]
+    theta = _facets_to_tiles(g, tRef[None, :, None, None] + 0.01 * rng.standard_normal((6, Nr, n, n)))
+    salt = _facets_to_tiles(g, 35.0 + 0.001 * rng.standard_normal((6, Nr, n, n)))
+    theta = g.exch(theta) * mC
+    salt = g.exch(salt) * mC
+    u = _facets_to_tiles(g, 0.1 * rng.standard_normal((6, Nr, n, n)))
+    v = _facets_to_tiles(g, 0.1 * rng.standard_normal((6, Nr, n, n)))
+    u, v = topo.exchange_uv(u, v, True)
+    u, v = u * g.f["maskW"], v * g.f["maskS"]
+    fu = _facets_to_tiles(g, 0.1 * rng.standard_normal((6, 1, n, n)))
+    fv = _facets_to_tiles(g, 0.1 * rng.standard_normal((6, 1, n, n)))
+    fu, fv = topo.exchange_uv(fu, fv, True)
+    params = dict(deltaTMom=dt, deltaTFreeSurf=dt, deltaTClock=dt, deltaTtracer=dt, abEps=0.1, rhoConst=1035.0,
+                  rhoNil=1035.0, gravity=9.81, gBaro=9.81, viscAhD=1.0e4, viscAhZ=1.0e4, viscA4D=0.0, viscA4Z=0.0,
+                  viscAr=1.0e-4, sideDragFactor=2.0, selectCoriScheme=0, vectorInvariantMomentum=1,
+                  selectVortScheme=1, selectKEscheme=0, momForcingOutAB=0, momDissip_In_AB=1, cg2dMaxIters=1000,
+                  cg2dUseMinResSol=0, nIter0=0, no_slip_sides=1, no_slip_bottom=1, exactConserv=1,
+                  tempStepping=1, tempAdvection=1, tempForcing=1, tempAdvScheme=2, tempVertAdvScheme=2,
+                  saltStepping=1, saltAdvection=1, saltForcing=1, saltAdvScheme=2, saltVertAdvScheme=2,
+                  diffKhT=0.0, diffKrT=1.0e-5, diffKhS=0.0, diffKrS=1.0e-5, ivdc_kappa=10.0, implicitDiffusion=1,
+                  usingCurvilinearGrid=1, rSphere=6370.0e3, integr_GeoPot=2, eosType=0, tAlpha=2.0e-4, sBeta=7.4e-4)
+    params.update(params_over or {})
+    state = {"theta": theta, "salt": salt, "uVel": u, "vVel": v, "tRef": tRef, "sRef": np.full(Nr, 35.0),
+             "fu": fu[:, 0], "fv": fv[:, 0]}
+    if params.get("nonlinFreeSurf", 0) > 0:
+        rF = g.f["rF"]
+        phiRef = np.zeros(2 * Nr + 1)
+        for k in range(Nr):
+            phiRef[2 * k + 1] = phiRef[0] + (rC[k] - rF[0]) * 9.81 * -1.0
+            phiRef[2 * k + 2] = phiRef[0] + (rF[k + 1] - rF[0]) * 9.81 * -1.0
+        state["phiRef"] = phiRef
+        for nm in ("h0FacC", "h0FacW", "h0FacS", "recip_Rcol", "rLowW", "rLowS", "rSurfW", "rSurfS"):
+            state[nm] = g.f[nm]
     return g, params, state

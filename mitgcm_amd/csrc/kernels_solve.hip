@@ -989,7 +989,9 @@ __global__ void __launch_bounds__(256) k_exchange_multi(Dims d, XFields x, const
 
 // EXCH2 C-grid vector exchange (EXCH2_UV_3D_RX, pkg/exch2/exch2_uv_3d_rx.template) as one
 // gather: entry h < nU writes u, the rest v; code = +-(src+1) with src indexing [u | v].
-// The maps only ever source interior points, so the gather runs in place.
+// The entries of one launch never read a point that the launch writes, so the gather runs in
+// place: sources are interior points, or -- on tiles as wide as the halo -- halo points whose
+// entries go into a launch of their own (model.hip uvPre).
 __global__ void __launch_bounds__(256) k_exchange_uv(Dims d, double *u, double *v, const long *__restrict__ map,
                                                      int nU, int nV) {
   const int h = (int)(blockIdx.x * blockDim.x + threadIdx.x);

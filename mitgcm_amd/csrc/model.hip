@@ -251,6 +251,13 @@ struct mgcm_model {
   // domain redundantly: CALC_R_STAR's EXCH_UV of the W/S factors covers remote tiles too)
   long *d_uvAll[2] = {nullptr, nullptr};
   int nUvUAll[2] = {0, 0}, nUvVAll[2] = {0, 0};
+  // Entries of those maps whose source is a halo point that the same exchange fills (tiles
+  // exactly as wide as the halo: the reference's second EXCH2_RX2_CUBE pass then copies a
+  // corner-halo value its first pass left alone, exch2.py).  The reference reads every source
+  // before it writes any halo, so such an entry takes the value from BEFORE the exchange: the
+  // entries are kept out of the maps above and run as a launch of their own ahead of them
+  // (uv_pre), [all tiles][withSigns]; they follow the main entries in the same buffer.
+  struct UvPre { const long *map = nullptr; int nU = 0, nV = 0; } uvPre[2][2];
   int *d_tileInfo = nullptr;
   // device scratch of mgcm_exchange_host (EXCH_*_RL on caller arrays)
   double *exchBuf[2] = {nullptr, nullptr};
@@ -408,20 +415,41 @@ static int upload_halo(mgcm_model *m) {
         long *&dm = all ? m->d_uvAll[w] : m->d_uv[w];
         if (dm) { hipFree(dm); dm = nullptr; }
         const long l0 = all ? 0 : lo, l1 = all ? N2 : hi;
-        std::vector<long> e;
-        int nu = 0, nv = 0;
+        const std::vector<long> &code = m->h_uv[w];   // [u | v], 0: the point is not written
+        auto srcOfCode = [](long c) { return (c > 0 ? c : -c) - 1; };
+        // early: the entry reads a point that the exchange writes (see uvPre)
+        auto early = [&](long c) { return c != 0 && code[(size_t)srcOfCode(c)] != 0; };
+        std::vector<long> e, pre;
+        int nu = 0, nv = 0, pu = 0, pv = 0;
         for (int c = 0; c < 2; c++)
           for (long q = l0; q < l1; q++) {
-            const long code = m->h_uv[w][(size_t)c * N2 + q];
-            if (code == 0) continue;
-            e.push_back(q); e.push_back(code);
+            const long cd = code[(size_t)c * N2 + q];
+            if (cd == 0) continue;
+            if (early(cd)) {
+              // one early launch is only right while no early entry reads another's target
+              if (early(code[(size_t)srcOfCode(cd)]))
+                return set_err("EXCH2 vector map: the halo of tile %ld copies a halo point that itself copies one "
+                               "(tiles narrower than the halo are not supported on the device)", q / m->d.n2 + 1);
+              if (m->d.nT < m->d.nTiles)
+                return set_err("EXCH2 vector map: tiles as narrow as the halo are not supported in tile-sharded runs");
+              pre.push_back(q); pre.push_back(cd);
+              (c ? pv : pu)++;
+              continue;
+            }
+            e.push_back(q); e.push_back(cd);
             (c ? nv : nu)++;
           }
         (all ? m->nUvUAll : m->nUvU)[w] = nu;
         (all ? m->nUvVAll : m->nUvV)[w] = nv;
+        m->uvPre[all][w] = mgcm_model::UvPre{};
+        const size_t nMain = e.size();
+        e.insert(e.end(), pre.begin(), pre.end());
         if (!e.empty()) {
           HIPCHK(hipMalloc(&dm, e.size() * sizeof(long)));
           HIPCHK(hipMemcpy(dm, e.data(), e.size() * sizeof(long), hipMemcpyHostToDevice));
+          m->uvPre[all][w].map = dm + nMain;
+          m->uvPre[all][w].nU = pu;
+          m->uvPre[all][w].nV = pv;
         }
       }
   }
@@ -1300,6 +1328,13 @@ int mgcm_set_uv_map(mgcm_model *m, const long *u1, const long *v1, const long *u
   return 0;
 }
 
+// The early entries of the vector map (mgcm_model::uvPre) on u, v: to be launched ahead of
+// every launch that applies d_uv / d_uvAll to the same pair; no launch where there are none.
+static hipError_t uv_pre(mgcm_model *m, const Dims &d, double *u, double *v, int nz, int w, bool all = false) {
+  const mgcm_model::UvPre &p = m->uvPre[all ? 1 : 0][w];
+  return launch_exchange_uv(d, u, v, p.map, p.nU, p.nV, nz, m->stream);
+}
+
 // EXCH_UV_XYZ_RL / EXCH_UV_XY_RL of a C-grid vector pair: the EXCH2 vector map when one
 // is installed, else the two components through the scalar (EXCH1) map.
 static int exchange_uv(mgcm_model *m, double *u, double *v, int nz, bool withSigns) {
@@ -1309,6 +1344,7 @@ static int exchange_uv(mgcm_model *m, double *u, double *v, int nz, bool withSig
     return 0;
   }
   const int w = withSigns ? 1 : 0;
+  HIPCHK(uv_pre(m, m->d, u, v, nz, w));
   HIPCHK(launch_exchange_uv(m->d, u, v, m->d_uv[w], m->nUvU[w], m->nUvV[w], nz, m->stream));
   return 0;
 }
@@ -1331,6 +1367,8 @@ static hipError_t calc_r_star(mgcm_model *m, bool fuseEtaH = false, int fromX = 
   if (stagEx) {
     XFields xw{};
     xw.p[0] = m->f.wVel; xw.nz[0] = m->d.Nr; xw.n = 1;
+    e = uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1);
+    if (e != hipSuccess) return e;
     e = launch_rstar_exmix(da, m->p, m->f, m->d_srcOf, fuseEtaH, fromX, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1],
                            m->nUvU[1], m->nUvV[1], xw, m->d_halo, m->nHalo, m->stream);
   } else
@@ -1338,6 +1376,8 @@ static hipError_t calc_r_star(mgcm_model *m, bool fuseEtaH = false, int fromX = 
   if (e != hipSuccess || !m->uvMap) return e;
   double *us[3] = {m->f.rStarFacW, m->f.rStarDhWDt, m->f.rStarExpW}, *vs[3] = {m->f.rStarFacS, m->f.rStarDhSDt,
                                                                                  m->f.rStarExpS};
+  for (int q = 0; q < 3; q++)
+    if ((e = uv_pre(m, da, us[q], vs[q], 1, 0, true)) != hipSuccess) return e;
   return launch_exchange_uv_pairs(da, us, vs, 3, m->d_uvAll[0], m->nUvUAll[0], m->nUvVAll[0], m->stream);
 }
 // sfp: k_sfp_rhs fused into the r* column pass (FORWARD_STEP on the whole domain only: in a
@@ -1448,6 +1488,11 @@ int mgcm_init(mgcm_model *m) {
   if (m->uvMap && ((m->p.tempStepping && mdScheme(m->p.tempAdvScheme)) || (m->p.saltStepping && mdScheme(m->p.saltAdvScheme)))) {
     if (!m->f.tileFace) return set_err("mgcm_init: multi-dimensional advection on EXCH2 needs the tile face table");
     if (m->d.OLx != m->d.OLy) return set_err("mgcm_init: cube multi-dimensional advection needs OLx = OLy");
+    // GAD_CHECK (gad_check.F:115-130): minOlSize = GAD_OlMinSize(1) * GAD_OlMinSize(3), the scheme's
+    // own 2 (DST3, DST3FL: gad_init_fixed.F:50-51) doubled under useCubedSphereExchange with
+    // useMultiDimAdvec (gad_init_fixed.F:178-181) -- the overlap-only passes update the halo
+    if (m->d.OLx < 4 || m->d.OLy < 4)
+      return set_err("mgcm_init: multi-dimensional advection on the cube needs OLx, OLy >= 4 (GAD_CHECK: Overlap Size too small)");
   }
   if (m->p.tempStepping && !okScheme(m->p.tempAdvScheme, "tempVertAdvScheme"))
     return set_err("mgcm_init: tempAdvScheme %d not implemented on the device", m->p.tempAdvScheme);
@@ -1690,6 +1735,7 @@ int mgcm_stagger_exchanges(mgcm_model *m) {
   if (m->uvMap) {
     XFields xw{};
     xw.p[0] = m->f.wVel; xw.nz[0] = m->d.Nr; xw.n = 1;
+    HIPCHK(uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1));
     TIMED(K_EXCH, launch_exchange_mixed(m->d, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1], m->nUvU[1], m->nUvV[1], xw,
                                         m->d_halo, m->nHalo, nullptr, m->stream));
   } else {
@@ -1740,6 +1786,7 @@ int mgcm_exchange_host(mgcm_model *m, double *u, double *v, int nz, int vector, 
   const int nh = m->d_haloAll ? m->nHaloAll : m->nHalo;
   if (vector && m->uvMap) {
     const int w = withSigns ? 1 : 0;
+    HIPCHK(uv_pre(m, m->d, m->exchBuf[0], m->exchBuf[1], nz, w, true));
     HIPCHK(launch_exchange_uv(m->d, m->exchBuf[0], m->exchBuf[1], m->d_uvAll[w], m->nUvUAll[w], m->nUvVAll[w], nz,
                               m->stream));
   } else {
@@ -2016,6 +2063,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
     } else if (m->uvMap) {   // u, v through the vector map and w through the scalar map, one launch
       XFields xw{};
       xw.p[0] = m->f.wVel; xw.nz[0] = m->d.Nr; xw.n = 1;
+      HIPCHK(uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1));
       TIMED(K_EXCH, launch_exchange_mixed(m->d, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1], m->nUvU[1], m->nUvV[1], xw,
                                           m->d_halo, m->nHalo, nullptr, m->stream));
     } else {
@@ -2026,10 +2074,11 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   }
   if (endFused) return 0;
   const XFields xEnd = blocking_fields(m, trEx ? 0 : 1);
-  if (m->uvMap)   // the vector pair and the scalar fields in one launch
+  if (m->uvMap) {   // the vector pair and the scalar fields in one launch
+    HIPCHK(uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1));
     TIMED(K_EXCH, launch_exchange_mixed(m->d, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1], m->nUvU[1], m->nUvV[1], xEnd,
                                         m->d_halo, m->nHalo, m->d_ctr, m->stream));
-  else
+  } else
     TIMED(K_EXCH, launch_exchange_multi(m->d, xEnd, m->d_halo, m->nHalo, m->d_ctr, m->stream));
   return 0;
 }

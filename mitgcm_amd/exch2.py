@@ -18,6 +18,12 @@ halo point, the interior point it copies (and, for vectors, from which
 component and with which sign).  The device applies the maps with one gather
 kernel per exchange (mgcm_set_halo_map / mgcm_set_uv_map); the oracle applies
 the same maps on the CPU.
+
+On tiles exactly as wide as the halo the C-grid vector maps hold a few entries whose
+source is itself a halo point (the outermost corner-halo column or row of a tile next
+to one that is filled only in the second pass): the reference copies that point's
+value from before the exchange, and so do the maps -- every gather reads the array as
+it was (the device runs those entries in a launch of their own, ahead of the others).
 """
 import numpy as np
 

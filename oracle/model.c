@@ -266,8 +266,9 @@ int oracle_set_exch2(OModel *m, const long *scal, const long *u1, const long *v1
 }
 
 /* pkg/exch2 exchanges as gathers: the maps are the composition of the reference's
- * two EXCH2_RX1/RX2 passes and corner fix-ups (mitgcm_amd/exch2.py); every source is
- * an interior point, so the gather may run in place. */
+ * two EXCH2_RX1/RX2 passes and corner fix-ups (mitgcm_amd/exch2.py).  Every value is read
+ * before any is written (tmp): on tiles as wide as the halo a few corner-halo points of the
+ * vector maps copy a halo point's value from before the exchange, as the reference does. */
 static void exch2_scalar(OModel *m, double *a, int nz) {
   const long N2 = m->n2 * m->nTiles;
   for (int k = 0; k < nz; k++) {

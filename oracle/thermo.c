@@ -338,6 +338,16 @@ static void tracer_integrate(OModel *m, const TracerSpec *c) {
         ((c->advScheme == 30 || c->advScheme == 33) && multiDim)) || c->vAdvScheme != c->advScheme) {
     fprintf(stderr, "oracle tracer_integrate: advection scheme %d/%d not restated\n", c->advScheme, c->vAdvScheme); abort();
   }
+  /* GAD_CHECK (gad_check.F:115-130), minOlSize: the scheme's own overlap (gad_init_fixed.F:44-51: 2 for
+   * U3, C4, DST3, DST3FL), doubled for multi-dimensional advection on the cube (:178-181) */
+  {
+    const int olMin = (c->advScheme == 2 ? 1 : 2) * ((multiDim && m->tileFace) ? 2 : 1);
+    if (c->advection && (OLx < olMin || OLy < olMin)) {
+      fprintf(stderr, "oracle tracer_integrate: Overlap Size OLx,OLy=%d %d too small: advection scheme %d needs %d\n",
+              OLx, OLy, c->advScheme, olMin);
+      abort();
+    }
+  }
 #pragma omp parallel if (m->nThreads > 1) num_threads(m->nThreads > 1 ? m->nThreads : 1)
   {
   double *gT = calloc(n3, 8), *kappaRT = calloc(n3, 8);

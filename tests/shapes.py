@@ -1,5 +1,5 @@
 """Helpers of the shape-sweep tests (test_oracle_shapes.py, test_gpu_shapes_cg2d.py,
-test_gpu_shapes_step.py): a barotropic box of free size, the dense reference of the CG2D
+test_gpu_shapes_step.py, test_gpu_shapes_cube.py): a barotropic box of free size, the dense reference of the CG2D
 solve, and the step loop that pins a device model bit for bit to the oracle.
 
 A plain module, not a conftest: the test files import it by name.
@@ -83,6 +83,24 @@ def untile(g, a):
     for t in range(g.nTiles):
         bi, bj = t % g.nSx, t // g.nSx
         out[:, bj * g.sNy:(bj + 1) * g.sNy, bi * g.sNx:(bi + 1) * g.sNx] = a[(t, slice(None)) + inner]
+    return out
+
+
+def cube_untile(g, a):
+    """Tile layout (nTiles, [nz,] ny, nx) on a pkg/exch2 cube of n x n facets ->
+    (6, nz, n, n), interiors only: tile t sits at rows tBy+1..tBy+sNy, columns
+    tBx+1..tBx+sNx of facet topo.face[t]."""
+    a = np.asarray(a)
+    if a.ndim == 3:
+        a = a[:, None]
+    topo = g.topo
+    (n, _), = set(topo.facet_dims)
+    out = np.zeros((len(topo.facet_dims), a.shape[1], n, n))
+    inner = g.sl(1, g.sNx, 1, g.sNy)
+    for t in range(g.nTiles):
+        tid = t + 1
+        y0, x0 = topo.tBy[tid], topo.tBx[tid]
+        out[topo.face[tid] - 1, :, y0:y0 + g.sNy, x0:x0 + g.sNx] = a[(t, slice(None)) + inner]
     return out
 
 

@@ -154,10 +154,11 @@ def test_box_mwg_ref_4_steps_bitexact(shape):
 STATE = ("uVel", "vVel", "wVel", "theta", "salt", "etaN", "etaH", "guNm1", "gvNm1", "gtNm1", "gsNm1", "totPhiHyd")
 
 
-@pytest.mark.parametrize("sNy,tiles", [(32, 6), (16, 12)])
-def test_cs32x15_mwg_ref_8_steps_bitexact(sNy, tiles):
-    """Config 3 on 6 tiles and on the experiment's own 12: 8 steps bit-identical to the plain
-    oracle of the same tiling.  The default device path's cg2d_init_res is printed against this
+@pytest.mark.parametrize("sNx,sNy,tiles", [(32, 32, 6), (32, 16, 12), (16, 8, 48)], ids=["32-6", "16-12", "16x8-48"])
+def test_cs32x15_mwg_ref_8_steps_bitexact(sNx, sNy, tiles):
+    """Config 3 on 6 tiles, on the experiment's own 12 and on the 48 tiles of 16 x 8 of the
+    reference's adjustment.cs-32x32x1 (more than 32 parts: not pinned to one XCD, a tile sum
+    of 48 partials): 8 steps bit-identical to the plain oracle of the same tiling.  The default device path's cg2d_init_res is printed against this
     run: its distance from the reference-order value (tests/test_gpu_cs32x15.py holds it to
     10.5 digits) is summation order only, since this run differs from it in nothing else.
     storePhiHyd4Phys = 1 on both sides: the state list holds totPhiHyd, which the device keeps
@@ -166,12 +167,12 @@ def test_cs32x15_mwg_ref_8_steps_bitexact(sNy, tiles):
     from mitgcm_amd import configs
     from oracle.harness import cs32x15_oracle
     m = configs.make_model(lambda: configs.global_ocean_cs32x15(
-        sNy=sNy, params_over={"cg2dRefOrder": 1, "storePhiHyd4Phys": 1}))
-    m_def = configs.make_model(lambda: configs.global_ocean_cs32x15(sNy=sNy))
+        sNx=sNx, sNy=sNy, params_over={"cg2dRefOrder": 1, "storePhiHyd4Phys": 1}))
+    m_def = configs.make_model(lambda: configs.global_ocean_cs32x15(sNx=sNx, sNy=sNy))
     try:
-        _assert_form(m, [32 * sNy] * tiles, 1)
+        _assert_form(m, [sNx * sNy] * tiles, 1 if tiles <= 32 else 0)
         assert m_def.cg2d_kernel() == "mwg"
-        o, g = cs32x15_oracle(sNy=sNy, params_over={"storePhiHyd4Phys": 1})
+        o, g = cs32x15_oracle(sNx=sNx, sNy=sNy, params_over={"storePhiHyd4Phys": 1})
         assert g.nTiles == tiles
         hist = _steps_bitexact(m, o, g, 8, STATE)
         worst = (99.0, None)

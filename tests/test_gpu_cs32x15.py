@@ -6,7 +6,8 @@ JMD95Z, GM/Redi in the advective form (GM_AdvForm: bolus stream-function, residu
 flow, extra-diagonal Redi fluxes), implicit diffusion, IVDC, monthly forcing with real
 fresh-water flux.
 
-Bars (device against the oracle on the same 6-tile layout):
+Bars (device against the oracle on the same layout: 6 tiles, and for the three per-routine
+tests also 96 tiles of 8 x 8 and 48 of 16 x 8, faces divided in x and y):
   * INITIALISE_VARIA's r* sequence on the cube: bit-exact;
   * DO_OCEANIC_PHYS (EOS, forcing, GM tensor incl. Kuz/Kvz and GM_PsiX/Y) and
     THERMODYNAMICS (C2 + bolus + extra-diagonal fluxes, implicit diffusion): bit-exact;
@@ -29,17 +30,24 @@ STATE = ("uVel", "vVel", "wVel", "theta", "salt", "gtNm1", "gsNm1", "etaN", "eta
          "aW2d", "aS2d", "aC2d", "pW", "pS", "pC")
 
 
-def _oracle(nsteps):
+# the per-routine tests' tilings (sNx, sNy): one tile per face; 96 tiles of 8 x 8 (interior,
+# one-edge and corner tiles); 48 of 16 x 8 -- a failing step of test_gpu_shapes_cube.py then
+# has a routine to its name
+TILINGS = [(32, 32), (8, 8), (16, 8)]
+TILING_IDS = ["%dx%d" % t for t in TILINGS]
+
+
+def _oracle(nsteps, tile=(32, 32)):
     from oracle.harness import cs32x15_oracle
-    o, g = cs32x15_oracle()
+    o, g = cs32x15_oracle(sNx=tile[0], sNy=tile[1])
     for _ in range(nsteps):
         o.forward_step()
     return o, g
 
 
-def _model():
+def _model(tile=(32, 32)):
     from mitgcm_amd import configs
-    return configs.make_model(configs.global_ocean_cs32x15)
+    return configs.make_model(configs.global_ocean_cs32x15, sNx=tile[0], sNy=tile[1])
 
 
 def _from_oracle(m, o, names):
@@ -61,9 +69,10 @@ def _cmp(m, o, names, region=None):
     return bad
 
 
-def test_cs32x15_init_rstar_bitexact():
-    o, g = _oracle(0)
-    m = _model()
+@pytest.mark.parametrize("tile", TILINGS, ids=TILING_IDS)
+def test_cs32x15_init_rstar_bitexact(tile):
+    o, g = _oracle(0, tile)
+    m = _model(tile)
     bad = _cmp(m, o, ("rStarFacC", "rStarFacW", "rStarFacS", "rStarExpC", "rStarExpW", "rStarExpS", "rStarDhCDt",
                       "hFacC", "hFacW", "hFacS", "recip_hFacC", "aW2d", "aS2d", "wVel", "PmEpR", "etaH", "etaN"))
     inner = (Ellipsis,) + g.sl(1, g.sNx + 1, 1, g.sNy + 1)
@@ -72,9 +81,10 @@ def test_cs32x15_init_rstar_bitexact():
     assert not bad, bad
 
 
-def test_cs32x15_oceanic_phys_gm_advform_and_thermodynamics_bitexact():
-    o, g = _oracle(2)
-    m = _model()
+@pytest.mark.parametrize("tile", TILINGS, ids=TILING_IDS)
+def test_cs32x15_oceanic_phys_gm_advform_and_thermodynamics_bitexact(tile):
+    o, g = _oracle(2, tile)
+    m = _model(tile)
     _from_oracle(m, o, STATE)
     m.thermodynamics()
     o.L.oracle_fields_load(o.h)
@@ -91,11 +101,12 @@ def test_cs32x15_oceanic_phys_gm_advform_and_thermodynamics_bitexact():
     assert not bad, bad
 
 
-def test_cs32x15_dynamics_vecinv_viscous_rstar_bitexact():
-    o, g = _oracle(2)
+@pytest.mark.parametrize("tile", TILINGS, ids=TILING_IDS)
+def test_cs32x15_dynamics_vecinv_viscous_rstar_bitexact(tile):
+    o, g = _oracle(2, tile)
     o.L.oracle_fields_load(o.h)
     o.L.oracle_oceanic_phys(o.h)
-    m = _model()
+    m = _model(tile)
     _from_oracle(m, o, STATE + ("rhoInSitu", "fu", "fv"))
     m.dynamics()
     o.L.oracle_dynamics(o.h)

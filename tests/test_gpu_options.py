@@ -204,12 +204,20 @@ def test_ocean90_cd_implicit_viscosity_4_steps_vs_oracle():
 # Options the device does not restate are refused at mgcm_init with the reason, never run
 # silently: ADAMS_BASHFORTH3 with momentum stepping or from
 # a pickup, the U3 / C4 schemes on a pkg/exch2 topology, a scheme the device does not carry.
-@pytest.mark.parametrize("case", ["ab3_momentum", "ab3_pickup", "c4_cube", "os7mp"])
+# Multi-dimensional DST3 on the cube at an overlap below the 4 GAD_CHECK demands (gad_check.F:115-130,
+# gad_init_fixed.F:178-181); EXCH2 tiles narrower than the halo (the vector map would copy halo
+# points in chains, csrc/model.hip uvPre).
+@pytest.mark.parametrize("case", ["ab3_momentum", "ab3_pickup", "c4_cube", "os7mp", "dst3_cube_ol3", "narrow_tiles"])
 def test_unsupported_options_refused(case):
     from mitgcm_amd import configs
     from mitgcm_amd._lib import MgcmError
 
     def cfg():
+        if case == "dst3_cube_ol3":
+            return configs.cube_synthetic(9, 2, OL=3, params_over=dict(
+                tempAdvScheme=33, tempVertAdvScheme=33, saltAdvScheme=33, saltVertAdvScheme=33))
+        if case == "narrow_tiles":
+            return configs.cube_synthetic(12, 2, 2, 3, OL=3)
         if case == "c4_cube":
             g, p, s = configs.global_ocean_cs32x15(sNy=32)[:3]
             p.update(tempAdvScheme=4, tempVertAdvScheme=4)
@@ -226,5 +234,6 @@ def test_unsupported_options_refused(case):
         configs.make_model(cfg)
     msg = str(e.value)
     want = {"ab3_momentum": "ADAMS_BASHFORTH3", "ab3_pickup": "ADAMS_BASHFORTH3", "c4_cube": "schemes 3 / 4",
-            "os7mp": "saltAdvScheme 7"}[case]
+            "os7mp": "saltAdvScheme 7", "dst3_cube_ol3": "needs OLx, OLy >= 4",
+            "narrow_tiles": "tiles narrower than the halo"}[case]
     assert want in msg, msg

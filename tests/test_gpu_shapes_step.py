@@ -10,6 +10,8 @@ oracle summing CG2D in the device's order).
   * tutorial_baroclinic_gyre (OL = 2) re-tiled into 62x62, 2x31, 31x2, 62x1 and 1x62 tiles;
   * the synthetic LLC at 9, 15, 6, 5 and 7 points per tile edge, 3, 5, 4, 1 and 31 levels and
     halos of 4, 3 and 2, in the flat and the k-march forms of the tracer and momentum kernels.
+The cube sphere (advect_cs, global_ocean.cs32x15 and a synthetic cube with their faces cut in
+x and y) has a file of its own, test_gpu_shapes_cube.py.
 One model of each family also runs the device MONITOR against the host restatement.
 The oracle's side of the re-tilings is pinned by test_oracle_shapes.py.
 """

@@ -87,13 +87,20 @@ def _w2_maps(topo, ldNb=None, ldT=None, mutate=None, want_rc=0, cubed=1):
 
 
 @pytest.mark.parametrize("kind,n,sNx,sNy,OL", [("cube", 32, 32, 32, 4), ("cube", 32, 32, 16, 4), ("cube", 32, 16, 16, 3),
-                                               ("llc", 30, 30, 30, 4), ("llc", 90, 90, 90, 4), ("llc", 30, 15, 30, 3)])
+                                               ("llc", 30, 30, 30, 4), ("llc", 90, 90, 90, 4), ("llc", 30, 15, 30, 3),
+                                               ("cube", 32, 16, 8, 4), ("cube", 32, 8, 8, 4), ("cube", 32, 8, 32, 4),
+                                               ("cube", 32, 4, 32, 4), ("cube", 12, 4, 6, 4), ("cube", 9, 3, 3, 3),
+                                               ("cube", 10, 5, 2, 2)])
 def test_exch2_maps_from_w2_arrays(kind, n, sNx, sNy, OL):
     """The library's pkg/exch2 map derivation from the W2_EXCH2_TOPOLOGY.h arrays
     (csrc/exch2_maps.hip, what the Fortran mirror hands it) reproduces, point for point, the
     maps of mitgcm_amd/exch2.py -- the restatement the cube and LLC tests pin to the
     reference's output.txt (solid-body.cs-32x32x1, advect_cs, global_ocean.cs32x15's grid) --
-    for the cube at 6, 12 and 24 tiles and the LLC at 13 and 26 tiles."""
+    for the cube at 6, 12 and 24 tiles and the LLC at 13 and 26 tiles; and for the cube with
+    its faces divided in x as well (tiles without a facet edge, with one, corner tiles): the
+    reference's own 48-tile layout of 16 x 8 (test_w2_default_cube_topology_pinned holds its
+    neighbour lists), 96 tiles of 8 x 8, tiles as narrow as the halo, and the small odd cubes
+    of test_gpu_shapes_cube.py."""
     from mitgcm_amd import exch2
     topo = exch2.cube_topology(n, sNx, sNy, OL) if kind == "cube" else exch2.llc_topology(n, sNx, sNy, OL)
     src, u1, v1, u0, v0 = _w2_maps(topo)

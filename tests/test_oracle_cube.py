@@ -1,7 +1,8 @@
 """Cubed-sphere path (pkg/exch2 + MOM_VECINV) pinned against the reference's committed
 output of verification/solid-body.cs-32x32x1 (6 faces of 32x32, one tile each):
   - mitgcm_amd/exch2.py maps: every halo value comes from an interior point (so the
-    device gather can run in place), all four exchange kinds;
+    device gather can run in place), all four exchange kinds; on tiles as wide as the halo
+    the C-grid vector maps alone also copy halo points, never in a chain;
   - the host grid (INI_CURVILINEAR_GRID + EXCH2 Z/B/A/C-grid exchanges + CALC_GRID_ANGLES)
     against the grid statistics output.txt prints at start-up;
   - the oracle (MOM_VECINV, EXCH2 vector exchanges, CG2D on the cube, C2 salt advection)
@@ -19,10 +20,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 
-@pytest.mark.parametrize("sN,sNy,OL", [(32, 32, 2), (32, 32, 4), (32, 16, 4), (16, 16, 3)])
-def test_exch2_maps_source_interior(sN, sNy, OL):
+# (n, sNx, sNy, OL); from (32, 16, 8, 4) on: faces divided in x as well (interior, one-edge
+# and corner tiles, the tilings of test_gpu_shapes_cube.py), tiles as narrow as the halo
+MAP_CASES = [(32, 32, 32, 2), (32, 32, 32, 4), (32, 32, 16, 4), (32, 16, 16, 3), (32, 16, 8, 4), (32, 8, 8, 4),
+             (32, 8, 32, 4), (32, 4, 32, 4), (12, 4, 6, 4), (9, 3, 3, 3), (10, 5, 2, 2)]
+
+
+@pytest.mark.parametrize("n,sN,sNy,OL", MAP_CASES,
+                         ids=["%d-%d-%d" % c[1:] if c[0] == 32 else "n%d-%d-%d-%d" % c for c in MAP_CASES])
+def test_exch2_maps_source_interior(n, sN, sNy, OL):
     from mitgcm_amd.exch2 import cube_topology
-    T = cube_topology(32, sN, sNy, OL)
+    T = cube_topology(n, sN, sNy, OL)
     N = T.nTiles * T.n2
     ar = np.arange(N)
     interior = np.array([T.is_interior(q) for q in range(N)])
@@ -32,7 +40,19 @@ def test_exch2_maps_source_interior(sN, sNy, OL):
         changed = ids != ar + base
         assert not changed[interior].any(), name          # interiors are never written
         src = ids[changed] % N
-        assert interior[src].all(), name                   # halos only copy interior points
+        if name not in ("u", "v") or min(sN, sNy) > OL:
+            assert interior[src].all(), name               # halos only copy interior points
+    # The C-grid vector maps on tiles exactly as wide as the halo: the reference's second
+    # EXCH2_RX2_CUBE pass copies, into a few corner-halo points, a halo value that only that
+    # same pass fills -- its value from before the exchange.  Such a source is itself filled
+    # from an interior point (no chains), so the device applies these entries in one launch
+    # ahead of the others (csrc/model.hip uvPre) and the oracle gathers from a copy.
+    u, _, v, _ = T.uv_ids(True)
+    full = np.concatenate([u, v])
+    written = full != np.arange(2 * N)
+    early = written & written[full]
+    assert early.any() == (min(sN, sNy) <= OL)
+    assert not written[full[full[early]]].any()
     # every halo point of the scalar exchange is filled on a cube (corner halos included)
     assert (T.scalar_ids()[~interior] != ar[~interior]).all()
 
