@@ -34,7 +34,7 @@ struct Dims {
     X(rSurfW) X(rSurfS) X(rLowW) X(rLowS) X(Ro_surf) X(R_low) X(rStarFacC) X(rStarFacW) X(rStarFacS) \
     X(rStarExpC) X(rStarExpW) X(rStarExpS) X(rStarDhCDt) X(rStarDhWDt) X(rStarDhSDt) X(PmEpR) X(dEtaHdt) \
     X(maskInW) X(maskInS) X(fCoriG) X(recip_rAz) X(recip_dxG) X(recip_dyG) X(etaHnm1) X(cg2d_r) X(cg2d_s) X(cg2d_q) \
-    X(cg2d_min) X(cg2d_y) X(cg2d_v) X(EmPmRnext)
+    X(cg2d_min) X(cg2d_y) X(cg2d_v) X(EmPmRnext) X(rStarFacCPrev) X(rStarFacWPrev) X(rStarFacSPrev)
 #define MG_F3D_LIST(X) X(hFacC) X(hFacW) X(hFacS) X(recip_hFacC) X(recip_hFacW) X(recip_hFacS) X(maskC) X(maskW) \
     X(maskS) X(uVel) X(vVel) X(wVel) X(theta) X(salt) X(gU) X(gV) X(guNm1) X(gvNm1) X(rhoInSitu) X(IVDConvCount) \
     X(gtNm1) X(thetaNext) X(gTscr) X(cpScr) X(phiHydC) X(saltNext) X(gsNm1) X(advScr1) X(advScr2) X(gAdv) \
@@ -140,6 +140,9 @@ struct Fields {
   double *cg2d_min;                   // its lowest-residual solution (cg2dUseMinResSol, cg2d.F:148-155, 338-369)
   double *cg2d_y, *cg2d_v;            // CG2D_SR's y = M r and v = A y (cg2d_sr.F:102-104)
   double *EmPmRnext;   // 2-D: the next step's EmPmR, between its hoisted DO_OCEANIC_PHYS and the end of the step (MG_FUSE_PIPE)
+  // 2-D: the r* factors as UPDATE_R_STAR's pass found them, kept for the next step's CALC_PHI_HYD in
+  // CALC_R_STAR's grid, which rewrites the factors themselves (MG_FUSE_PHIP)
+  double *rStarFacCPrev, *rStarFacWPrev, *rStarFacSPrev;
   // the 2-D and 3-D arenas (MG_F2D_LIST / MG_F3D_LIST order)
   double *a2, *a3;
 };
@@ -258,7 +261,7 @@ inline size_t mg_colf_lds(int Nr, int nc, int nArr) { return (size_t)nArr * Nr *
   } while (0)
 inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + nc - 1) / nc); }
 // Launch fusions of FORWARD_STEP, each switchable for A/B runs: MGCM_STEP_FUSE = bit mask of
-// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
+// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
 // MG_FUSE_ETA EXCH(cg2d_x) + etaN in the single-workgroup CG2D, MG_FUSE_PHI CALC_PHI_HYD +
 // del2uv in one grid, MG_FUSE_END CALC_R_STAR + the blocking exchanges in one grid,
 // MG_FUSE_PHYS DO_OCEANIC_PHYS + CALC_PHI_HYD in one column pass (bit-identical, but on LLC-90
@@ -280,15 +283,18 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 // DO_STAGGER_FIELDS_EXCHANGES' u, v, w in one grid (k_rstar_exmix: the staggered cube),
 // MG_FUSE_PIPE the next step's DO_OCEANIC_PHYS in this step's UPDATE_R_STAR grid and its
 // GMREDI_CALC_TENSOR in this step's correction-step grid (config 2's fold, calls of
-// MG_PIPE_MIN_STEPS steps or more; one_step's StepMode, model.hip).
+// MG_PIPE_MIN_STEPS steps or more; one_step's StepMode, model.hip), MG_FUSE_PHIP (with
+// MG_FUSE_PIPE) the next step's CALC_PHI_HYD and del2uv in this step's CALC_R_STAR + exchange grid
+// (k_rstar_exch_phi, kernels_step.hip): the pipelined step then starts at the momentum launch.
 enum { MG_FUSE_SFP = 1, MG_FUSE_ETA = 2, MG_FUSE_PHI = 4, MG_FUSE_END = 8, MG_FUSE_PHYS = 16, MG_FUSE_ETAA = 32,
        MG_FUSE_TREX = 64, MG_FUSE_DT = 128, MG_FUSE_ETAX = 256, MG_FUSE_TCG = 512, MG_FUSE_OPE = 1024,
-       MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384 };
+       MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384, MG_FUSE_PHIP = 32768 };
 inline bool mg_fuse_on(int bit) {
   // read per call (tests switch it per model)
   const int mask = getenv("MGCM_STEP_FUSE") ? atoi(getenv("MGCM_STEP_FUSE"))
                                             : MG_FUSE_SFP | MG_FUSE_PHI | MG_FUSE_END | MG_FUSE_DT | MG_FUSE_ETAX |
-                                                MG_FUSE_OPE | MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE;
+                                                MG_FUSE_OPE | MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE |
+                                                MG_FUSE_PHIP;
   return (mask & bit) != 0;
 }
 // Horizontal launch fusion of two independent latency-bound kernels into one grid: on the

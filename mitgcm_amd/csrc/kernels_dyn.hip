@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "phys.h"
+#include "rstar.h"
 #include <cstring>
 #include <cstdio>
 #include <type_traits>
@@ -44,7 +45,11 @@ __device__ __forceinline__ double h0facz(const Dims &d, const Params &p, const F
 // cosFac = 1, no OBCS) for one (i,j,k) of 2-OL..sN+OL-1 (0 elsewhere, as the zeroed v4F):
 // the Laplacians of u and v the biharmonic viscous fluxes difference, with the no-slip
 // side-wall term from the rest-state h0Fac (NONLIN_FRSURF).
-__device__ __forceinline__ void del2uv_body(const Dims &d, const Params &p, const Fields &f, int lb) {
+// HO (MG_FUSE_PHIP): the pass of the next step inside this step's end-of-step exchange grid, which
+// is filling the halos of u and v: every u, v is read at its exchange source (mg_at_source3).
+template <bool HO = false>
+__device__ __forceinline__ void del2uv_body(const Dims &d, const Params &p, const Fields &f, int lb,
+                                            const long *__restrict__ srcOf = nullptr) {
   MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   const long q3 = MG_I3(d, i, j, k, t);
@@ -54,8 +59,12 @@ __device__ __forceinline__ void del2uv_body(const Dims &d, const Params &p, cons
     return;
   }
   const double drF = f.drF[k - 1];
-#define U(ii, jj) f.uVel[MG_I3(d, ii, jj, k, t)]
-#define V(ii, jj) f.vVel[MG_I3(d, ii, jj, k, t)]
+  // the five points u and v are read at: (i,j), (i-1,j), (i+1,j), (i,j-1), (i,j+1)
+  auto uv3 = [&](int ii, int jj) { return HO ? mg_at_source3(d, srcOf, ii, jj, k, t) : MG_I3(d, ii, jj, k, t); };
+  const long qv[5] = {uv3(i, j), uv3(i - 1, j), uv3(i + 1, j), uv3(i, j - 1), uv3(i, j + 1)};
+  auto qvAt = [&](int ii, int jj) { return qv[jj == j ? (ii == i ? 0 : ii < i ? 1 : 2) : (jj < j ? 3 : 4)]; };
+#define U(ii, jj) f.uVel[HO ? qvAt(ii, jj) : MG_I3(d, ii, jj, k, t)]
+#define V(ii, jj) f.vVel[HO ? qvAt(ii, jj) : MG_I3(d, ii, jj, k, t)]
 #define G2(a, ii, jj) f.a[MG_I2(d, ii, jj, t)]
 #define G3(a, ii, jj) f.a[MG_I3(d, ii, jj, k, t)]
   {
@@ -114,9 +123,19 @@ __global__ void __launch_bounds__(256) k_del2uv(Dims d, Params p, Fields f) { de
 // (k_phys_phi: DO_OCEANIC_PHYS and CALC_PHI_HYD in one launch where nothing between them
 // reads DO_OCEANIC_PHYS's output at a neighbour -- no GM/Redi tensor -- and phi is not
 // already fused with del2uv)
-template <bool PHYS = false>
+// HO (MG_FUSE_PHIP, r* only): the pass of the NEXT step inside this step's last grid, beside
+// CALC_R_STAR + UPDATE_ETAH and the blocking exchanges (k_rstar_exch_phi, kernels_step.hip).  The
+// same expression trees on the values the next step's own pass would read:
+//   - uVel, vVel of the QH buoyancy terms at their exchange sources (mg_at_source3);
+//   - rStarFacC and rStarDh{C,W,S}Dt, which CALC_R_STAR's blocks are storing, formed here by the
+//     same expressions from the factors kept in rStarFac*Prev (rstar.h r_star_next_point);
+//   - rhoInSitu, h0Fac and the geometry in place (nothing in the grid writes them);
+//   - totPhiHyd is stored on the ring 0 / sN+1 too, so a step that carries this pass leaves
+//     totPhiHyd out of its exchange (model.hip one_step).
+template <bool PHYS = false, bool HO = false>
 __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, const Fields &f, int nc, int lb,
-                                             const int *iterPtr = nullptr) {
+                                             const int *iterPtr = nullptr, const long *__restrict__ srcOf = nullptr,
+                                             int fromX = 0) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   MG_COLF_LB(PHYS ? 1 - d.OLx : -1, PHYS ? d.nx : d.sNx + 3, PHYS ? 1 - d.OLy : -1, PHYS ? d.ny : d.sNy + 3, nc, lb)
   const int Nr = d.Nr, NS = Nr * NC_;
@@ -127,19 +146,42 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
   const bool ring = inPhi && i >= 0 && j >= 0;
   const double recip_rhoConst = 1.0 / p.rhoConst;
   const long q2 = MG_I2(d, i, j, t);
+  double hoFacC = 0.0, hoDhC = 0.0, hoDhW = 0.0, hoDhS = 0.0;   // HO: the column's new r* factor and rates
+  // ... and the serial thread's d0 of the west and south neighbours: formed before the barrier by
+  // two other level slots of the column (other waves) and handed over in the first two rows of
+  // sPh, which nothing else touches until the serial part (Nr >= 2; else the serial thread forms them)
+  const bool hoStash = HO && Nr >= 2 && KW_ >= 4;
+  auto hoD0 = [&](long r) {
+    double fc_ = 0.0, c_ = 0.0, w_ = 0.0, s_ = 0.0;
+    if constexpr (HO) r_star_next_point<false>(d, p, f, srcOf, r, fromX, fc_, c_, w_, s_);
+    return c_ * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
+  };
+  // (HO: the column's factor and rates are formed inside the first level's pass, after that
+  // level's own loads are issued, so that the two latency chains overlap)
+  bool hoHave = false;
   if (valid) MG_COLF_K(k) {
     const int me = (k - 1) * NC_ + cc;
     double dRlocM = 0.5 * f.drC[k - 1];
     if (k == 1) dRlocM = f.rF[0] - f.rC[0];
     const double dRlocP = (k == Nr) ? (f.rC[k - 1] - f.rF[k]) : 0.5 * f.drC[k];
     const long q3 = MG_I3(d, i, j, k, t);
+    double hoOp[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // HO: the operands of the dWtrans terms
+    if constexpr (HO) {
+      if (rstar) {
+        hoOp[0] = f.drF[k - 1]; hoOp[1] = f.h0FacC[q3]; hoOp[2] = f.rA[q2];
+        if (ring) { hoOp[3] = f.h0FacW[q3]; hoOp[4] = f.rAw[q2]; hoOp[5] = f.h0FacS[q3]; hoOp[6] = f.rAs[q2]; }
+      }
+    }
     double a;
     if constexpr (PHYS) a = oceanic_phys_point(d, p, f, iterPtr, i, j, k, t);
     else a = f.rhoInSitu[q3];
     if (qh) {
       const double scalingFactor = p.rhoConst * p.gravitySign * (1.0 / p.gravity);
-      const double u0 = f.uVel[q3], u1 = f.uVel[MG_I3(d, i + 1, j, k, t)];
-      const double v0 = f.vVel[q3], v1 = f.vVel[MG_I3(d, i, j + 1, k, t)];
+      const long qc = HO ? mg_at_source3(d, srcOf, i, j, k, t) : q3;
+      const long qe = HO ? mg_at_source3(d, srcOf, i + 1, j, k, t) : MG_I3(d, i + 1, j, k, t);
+      const long qn = HO ? mg_at_source3(d, srcOf, i, j + 1, k, t) : MG_I3(d, i, j + 1, k, t);
+      const double u0 = f.uVel[qc], u1 = f.uVel[qe];
+      const double v0 = f.vVel[qc], v1 = f.vVel[qn];
       double gW = 0.0;
       if (p.select3dCoriScheme >= 1) gW = f.fCoriCos[q2] * (1.0 * 0.5 * (u0 + u1) - 0.0 * 0.5 * (v0 + v1));
       if (p.useNHMTerms) gW = gW + ((u0 * u0 + u1 * u1) + (v0 * v0 + v1 * v1)) * 0.5 * p.recip_rSphere;
@@ -149,16 +191,41 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
     sM[me] = dRlocM * p.gravity * a * recip_rhoConst;
     sP[me] = dRlocP * p.gravity * a * recip_rhoConst;
     if (rstar) {
-      const double drF = f.drF[k - 1];
-      sC[me] = f.rStarDhCDt[q2] * drF * f.h0FacC[q3] * f.rA[q2];
-      if (ring) {
-        sU[me] = f.rStarDhWDt[q2] * drF * f.h0FacW[q3] * f.rAw[q2];
-        sV[me] = f.rStarDhSDt[q2] * drF * f.h0FacS[q3] * f.rAs[q2];
+      if constexpr (HO) {
+        if (!hoHave) {
+          r_star_next_point<true>(d, p, f, srcOf, q2, fromX, hoFacC, hoDhC, hoDhW, hoDhS);
+          hoHave = true;
+        }
+        sC[me] = hoDhC * hoOp[0] * hoOp[1] * hoOp[2];
+        if (ring) {
+          sU[me] = hoDhW * hoOp[0] * hoOp[3] * hoOp[4];
+          sV[me] = hoDhS * hoOp[0] * hoOp[5] * hoOp[6];
+        }
+      } else {
+        const double drF = f.drF[k - 1];
+        sC[me] = f.rStarDhCDt[q2] * drF * f.h0FacC[q3] * f.rA[q2];
+        if (ring) {
+          sU[me] = f.rStarDhWDt[q2] * drF * f.h0FacW[q3] * f.rAw[q2];
+          sV[me] = f.rStarDhSDt[q2] * drF * f.h0FacS[q3] * f.rAs[q2];
+        }
+      }
+    }
+  }
+  if constexpr (HO) {
+    if (valid && rstar) {
+      if (!hoHave && kk == 0) r_star_next_point<true>(d, p, f, srcOf, q2, fromX, hoFacC, hoDhC, hoDhW, hoDhS);
+      if (hoStash && ring) {
+        if (kk == KW_ / 4) sPh[cc] = hoD0(q2 - 1);
+        if (kk == KW_ / 2) sPh[NC_ + cc] = hoD0(q2 - d.nx);
       }
     }
   }
   __syncthreads();
   if (valid && kk == 0) {
+    double hoW = 0.0, hoS = 0.0;
+    if constexpr (HO) {
+      if (rstar && hoStash && ring) { hoW = sPh[cc]; hoS = sPh[NC_ + cc]; }
+    }
     double phF = 0.0;
     for (int k2 = 1; k2 <= Nr; k2++) {
       const int s2 = (k2 - 1) * NC_ + cc;
@@ -167,7 +234,15 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
       sPh[s2] = phC;
     }
     if (rstar) {
-      auto d0 = [&](long r) { return f.rStarDhCDt[r] * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r]; };
+      auto d0 = [&](long r) {
+        if constexpr (HO) {
+          if (r == q2) return hoDhC * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
+          if (hoStash) return r == q2 - 1 ? hoW : hoS;
+          return hoD0(r);
+        } else {
+          return f.rStarDhCDt[r] * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
+        }
+      };
       double c = d0(q2);
       double u = ring ? 0.5 * (d0(q2 - 1) + c) : 0.0, v = ring ? 0.5 * (d0(q2 - d.nx) + c) : 0.0;
       for (int k2 = 1; k2 <= Nr; k2++) {   // value seen by MOM_CALC_RTRANS(k2): levels 1..k2-1 removed
@@ -200,7 +275,8 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
         double tot;
         if (rstar && p.nonlinFreeSurf >= 4) {
           const double dPhiRef = (f.Ro_surf[q2] - f.rC[k - 1]) * p.gravity;
-          tot = phC * f.rStarFacC[q2] + fmax(dPhiRef, 0.0) * (f.rStarFacC[q2] - 1.0) + 0.0;
+          if constexpr (HO) tot = phC * hoFacC + fmax(dPhiRef, 0.0) * (hoFacC - 1.0) + 0.0;
+          else tot = phC * f.rStarFacC[q2] + fmax(dPhiRef, 0.0) * (f.rStarFacC[q2] - 1.0) + 0.0;
         } else {
           tot = phC + f.Bo_surf[q2] * f.etaN[q2] + 0.0;
         }

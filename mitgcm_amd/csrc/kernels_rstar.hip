@@ -11,91 +11,12 @@
 // EXCH copies values that are computed by the same expression as the source's.
 #include "common.h"
 #include "phys.h"
+#include "rstar.h"
 #include "ucg2d.h"
 
 namespace mgcm {
 
-// CALC_R_STAR (calc_r_star.F:95-298) in one pass per 2-D point q: the new factors on
-// the reference's ranges (:111-150, rStarAreaWeight = .TRUE.), EXCH_XY_RL(rStarFacC) +
-// EXCH_UV_XY_RL(rStarFacW,S) by evaluating a halo point's factor at its interior source
-// (lat-lon / single facet: scalar copies), then rStarDh*Dt = (Fac - Fac_old)/dtFS and
-// rStarExp = Fac/Fac_old (:283-298).  Each thread reads and writes only its own point's
-// factors, so the old values need no second buffer.
-// The new etaH of k_exch_etaH at point q: EXCH_XY_RL of the eta k_corr_cont left in cg2d_b
-// (the interior source of a halo point; the point itself inside; etaN where neither --
-// fromX: the etaN SOLVE_FOR_PRESSURE's EXCH(cg2d_x) + etaN = recip_Bo*cg2d_x leaves there,
-// recip_Bo*cg2d_x of the point itself, when that launch was skipped, see one_step).
-__device__ __forceinline__ double eta_exch(const Dims &d, const Fields &f, const long *srcOf, long q, int fromX) {
-  const long sq = srcOf[q];
-  if (sq >= 0) return f.cg2d_b[sq];
-  const long l = q % d.n2;
-  const int i = (int)(l % d.nx) - d.OLx + 1, j = (int)(l / d.nx) - d.OLy + 1;
-  if (i >= 1 && i <= d.sNx && j >= 1 && j <= d.sNy) return f.cg2d_b[q];
-  return fromX ? f.recip_Bo[q] * f.cg2d_x[q] : f.etaN[q];
-}
-
-// fuseEtaH: k_exch_etaH in the same pass (the FORWARD_STEP order exch_etaH -> CALC_R_STAR):
-// each thread stores its own point's etaN, etaH, etaHnm1 (and PmEpR) and takes the etaH of
-// the neighbours it reads from eta_exch, the same values k_exch_etaH stores.  The only
-// cross-thread location both read and written is etaN at points neither interior nor
-// mapped, which is rewritten with the value it holds.
-// empNext (MG_FUSE_PIPE, with FUSE): the next step's DO_OCEANIC_PHYS ran earlier in this step
-// and left its EmPmR in EmPmRnext (phys.h); this pass, the step's last reader of EmPmR, moves
-// it over once it has formed PmEpR -- each thread its own point.
-template <bool FUSE>
-__device__ __forceinline__ void calc_r_star_body(const Dims &d, const Params &p, const Fields &f,
-                                                 const long *__restrict__ srcOf, int lb, int fromX, int empNext = 0) {
-  const long q = (long)lb * blockDim.x + threadIdx.x;
-  if (q >= d.n2 * d.nTiles) return;
-  const int t = (int)(q / d.n2);
-  if (t < d.t0 || t >= d.t0 + d.nT) return;
-  if constexpr (FUSE) {   // k_exch_etaH (kernels_solve.hip), atInit = 0
-    if (p.nonlinFreeSurf > 0 && p.useRealFreshWaterFlux) f.PmEpR[q] = -f.EmPmR[q];
-    if (empNext) f.EmPmR[q] = f.EmPmRnext[q];
-    const double x = eta_exch(d, f, srcOf, q, fromX);
-    f.etaHnm1[q] = f.etaH[q];
-    f.etaN[q] = x;
-    f.etaH[q] = x;
-  }
-  const long sq = srcOf[q], r = sq >= 0 ? sq : q;   // where the new value is computed
-  const long l = r % d.n2;
-  const int i = (int)(l % d.nx) - d.OLx + 1, j = (int)(l / d.nx) - d.OLy + 1;
-  auto eta = [&](long qq) { return FUSE ? eta_exch(d, f, srcOf, qq, fromX) : f.etaH[qq]; };
-  const double oc = f.rStarFacC[q], ow = f.rStarFacW[q], os = f.rStarFacS[q];
-  double fc = oc, fw = ow, fs = os;
-  if (i >= 0 && i <= d.sNx + 1 && j >= 0 && j <= d.sNy + 1)   // kSurfC <= Nr <=> maskInC = 1
-    fc = (f.maskInC[r] != 0.0) ? (eta(r) + f.Ro_surf[r] - f.R_low[r]) * f.recip_Rcol[r] : 1.0;
-  // W/S factors: at the EXCH1 source as above, or (EXCH2 topology) in place on the
-  // reference's ranges, their halos then refilled through the vector map (calc_r_star())
-  const long rv = p.cubeCorners ? q : r;
-  const long lv = rv % d.n2;
-  const int iv = (int)(lv % d.nx) - d.OLx + 1, jv = (int)(lv / d.nx) - d.OLy + 1;
-  if (iv >= 1 && iv <= d.sNx + 1 && jv >= 1 && jv <= d.sNy) {
-    if (f.maskInW[rv] != 0.0) {
-      const double tmp = f.rSurfW[rv] - f.rLowW[rv];
-      fw = (0.5 * (eta(rv - 1) * f.rA[rv - 1] + eta(rv) * f.rA[rv]) * f.recip_rAw[rv] + tmp) / tmp;
-    } else {
-      fw = 1.0;
-    }
-  }
-  if (iv >= 1 && iv <= d.sNx && jv >= 1 && jv <= d.sNy + 1) {
-    if (f.maskInS[rv] != 0.0) {
-      const double tmp = f.rSurfS[rv] - f.rLowS[rv];
-      fs = (0.5 * (eta(rv - d.nx) * f.rA[rv - d.nx] + eta(rv) * f.rA[rv]) * f.recip_rAs[rv] + tmp) / tmp;
-    } else {
-      fs = 1.0;
-    }
-  }
-  f.rStarFacC[q] = fc;
-  f.rStarFacW[q] = fw;
-  f.rStarFacS[q] = fs;
-  f.rStarDhCDt[q] = (fc - oc) / p.deltaTFreeSurf;
-  f.rStarDhWDt[q] = (fw - ow) / p.deltaTFreeSurf;
-  f.rStarDhSDt[q] = (fs - os) / p.deltaTFreeSurf;
-  f.rStarExpC[q] = fc / oc;
-  f.rStarExpW[q] = fw / ow;
-  f.rStarExpS[q] = fs / os;
-}
+// CALC_R_STAR's per-point pass: rstar.h calc_r_star_body
 template <bool FUSE>
 __global__ void __launch_bounds__(256) k_calc_r_star(Dims d, Params p, Fields f, const long *__restrict__ srcOf, int fromX) {
   calc_r_star_body<FUSE>(d, p, f, srcOf, (int)blockIdx.x, fromX);
@@ -147,13 +68,16 @@ __global__ void __launch_bounds__(256) k_rstar_exmix(Dims d, Params p, Fields f,
 // PH (MG_FUSE_PIPE): the next step's DO_OCEANIC_PHYS on the first nbPh logical blocks
 // (phys.h phys_hoist_body: it reads the new theta and salt, totPhiHyd, h0FacC*rStarFacC and
 // EmPmR, none of which this pass writes, and writes nothing this pass reads)
-template <bool SFP, bool PH>
+// PH = 2 (MG_FUSE_PHIP): also keeps the factors it read in rStarFac{C,W,S}Prev, each column its
+// own point -- the old factors of this step's CALC_R_STAR, for the next step's CALC_PHI_HYD riding
+// in CALC_R_STAR's grid (rstar.h r_star_next_point)
+template <bool SFP, int PH>
 __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, Fields f, int nc, int opIn,
                                                               const long *__restrict__ srcOf, int nbPc,
                                                               const int *iterPtr, int nbPh) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int lb = mg_xcd_block();
-  if constexpr (PH) {
+  if constexpr (PH != 0) {
     if (lb < nbPh) { phys_hoist_body(d, p, f, iterPtr, srcOf, lb); return; }
     lb -= nbPh;
   }
@@ -168,6 +92,9 @@ __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, 
   const bool inner = i >= 1 && i <= d.sNx && j >= 1 && j <= d.sNy;
   if (valid) {
     const double fc = f.rStarFacC[q], fw = f.rStarFacW[q], fs = f.rStarFacS[q];
+    if constexpr (PH == 2) {
+      if (kk == 0) { f.rStarFacCPrev[q] = fc; f.rStarFacWPrev[q] = fw; f.rStarFacSPrev[q] = fs; }
+    }
     double fwE = 0.0, fsN = 0.0;
     if (SFP && inner) { fwE = f.rStarFacW[MG_I2(d, i + 1, j, t)]; fsN = f.rStarFacS[MG_I2(d, i, j + 1, t)]; }
     MG_COLF_K(k) {
@@ -264,25 +191,29 @@ hipError_t launch_rstar_exmix(const Dims &d, const Params &p, const Fields &f, c
 
 // opEarly: the operator and preconditioner were built beside DYNAMICS (launch_dyn_thermo);
 // pcHere (with opEarly): only the operator was, the preconditioner rides in this launch
-// iterPtr non-null: the next step's DO_OCEANIC_PHYS rides at the head of the grid
+// iterPtr non-null: the next step's DO_OCEANIC_PHYS rides at the head of the grid; keepFac with it:
+// the factors are also kept in rStarFac*Prev
 hipError_t launch_update_r_star_cg2d(const Dims &d, const Params &p, const Fields &f, const long *srcOf, hipStream_t s,
-                                     bool sfp, bool opEarly, bool pcHere, const int *iterPtr) {
+                                     bool sfp, bool opEarly, bool pcHere, const int *iterPtr, bool keepFac) {
   const long n = d.n2 * d.nTiles;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const long ncol = (long)d.nx * d.ny * d.nT;
   const int nArr = sfp ? 6 : 2;
   const int nc = mg_colf_nc(ncol, d.Nr, nArr);
-  auto kPlain = k_update_r_star_cg2d_a<false, false>, kSfp = k_update_r_star_cg2d_a<true, false>,
-       kSfpPhys = k_update_r_star_cg2d_a<true, true>;
+  auto kPlain = k_update_r_star_cg2d_a<false, 0>, kSfp = k_update_r_star_cg2d_a<true, 0>,
+       kSfpPhys = k_update_r_star_cg2d_a<true, 1>, kSfpPhysKeep = k_update_r_star_cg2d_a<true, 2>;
   MG_ALLOW_LDS(kPlain);
   MG_ALLOW_LDS(kSfp);
   const int nbPc = (opEarly && pcHere && p.nonlinFreeSurf > 2) ? (int)nb : 0;
   if (iterPtr) {
     if (!sfp) return hipErrorInvalidValue;   // (one_step pipelines only the fused right-hand side's layout)
     MG_ALLOW_LDS(kSfpPhys);
+    MG_ALLOW_LDS(kSfpPhysKeep);
     const int nbPh = phys_hoist_blocks(d);
-    hipLaunchKernelGGL(kSfpPhys, dim3(mg_colf_blocks(ncol, nc) + (unsigned)(nbPc + nbPh)), dim3(256),
+    hipLaunchKernelGGL(keepFac ? kSfpPhysKeep : kSfpPhys, dim3(mg_colf_blocks(ncol, nc) + (unsigned)(nbPc + nbPh)), dim3(256),
                        mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc, opEarly ? 0 : 1, srcOf, nbPc, iterPtr, nbPh);
+  } else if (keepFac) {
+    return hipErrorInvalidValue;
   } else
     hipLaunchKernelGGL(sfp ? kSfp : kPlain, dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbPc), dim3(256),
                        mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc, opEarly ? 0 : 1, srcOf, nbPc, (const int *)nullptr, 0);

@@ -25,6 +25,7 @@
 #include "kernels_dyn.hip"
 #include "kernels_thermo.hip"
 #include "ucg2d.h"
+#include "rstar.h"
 
 namespace mgcm {
 
@@ -257,9 +258,11 @@ hipError_t launch_tracer_hpair(const Dims &d, const Params &p, const Fields &f, 
 // (after DO_OCEANIC_PHYS; dyn_thermo_fusable must hold).  srcOf != nullptr (default layout,
 // nonlinFreeSurf > 2, every tile): UPDATE_CG2D in the first two grids as well (ucg2d.h), and
 // launch_update_r_star_cg2d then runs with opEarly.  gmHere = false (the default layout only):
-// GMREDI_CALC_TENSOR of this step ran in the previous step's grids
+// GMREDI_CALC_TENSOR of this step ran in the previous step's grids.  l1Here = false (with it):
+// so did CALC_PHI_HYD and del2uv (k_rstar_exch_phi, or launch_phi_del2 at the head of a call) --
+// two launches
 hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, const TracerArgs &aT, const TracerArgs &aS,
-                             const int *iterPtr, hipStream_t s, const long *srcOf, bool gmHere) {
+                             const int *iterPtr, hipStream_t s, const long *srcOf, bool gmHere, bool l1Here) {
   const dim3 blk(256);
   // front: phi's column frame (launch_phi_hyd's columns and LDS), del2uv's and the tracers' planes
   int ncPhi, nArrPhi, nbPhi;
@@ -274,7 +277,8 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
     // operator's blocks best
     const int nbU = srcOf ? ucg2d_blocks(d) : 0;
     const int nbOp1 = 0, nbPc2 = 0, nbOp2 = nbU, nbPc3 = nbU;
-    launch_l1(d, p, f, nbDel, s, nbOp1, gmHere);
+    if (l1Here) launch_l1(d, p, f, nbDel, s, nbOp1, gmHere);
+    else if (gmHere) return hipErrorInvalidValue;
     const bool ff4 = mom_ff4_on(true);
     const int nbMom = ff4 ? mom_ff4_blocks(d) : 2 * (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
     auto l2 = ff4 ? k_dt_l2<true, true> : k_dt_l2<true, false>;
@@ -289,7 +293,7 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
                        aS, iterPtr, ncTr, nbCd, nbImp, srcOf, nbPc3, dt_long_first());
     return hipGetLastError();
   }
-  if (srcOf || !gmHere) return hipErrorInvalidValue;   // (the operator rides, and the tensor leaves, only in the default layout)
+  if (srcOf || !gmHere || !l1Here) return hipErrorInvalidValue;   // (the operator rides, and the tensor and grid 1 leave, only in the default layout)
   MG_ALLOW_LDS(k_dt_front<true>);
   hipLaunchKernelGGL(k_dt_front<true>, dim3((unsigned)(nbPhi + nbDel + 2 * nbTr)), blk,
                      mg_colf_lds(d.Nr, ncPhi, nArrPhi), s, d, p, f, aT, aS, iterPtr, ncPhi, nbPhi, nbDel, nbTr);
@@ -304,6 +308,62 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_mom_tail(d, p, f, iterPtr, s);
+}
+
+// ---- the next step's CALC_PHI_HYD and del2uv in the step's last grid (MG_FUSE_PHIP) -------------
+// Of step n, the first launch of step n+1 (k_dt_l1 without the tensor: CALC_PHI_HYD | del2uv)
+// needs only what step n's last launch (k_rstar_exch) produces: the halos of u and v, each a copy
+// of the value at its exchange source, and the r* factors, each a few flops on the eta the
+// correction step left.  So it runs as further logical blocks of that grid, reading u and v at
+// the sources and forming the factors itself (kernels_dyn.hip phi_hyd_body<.., HO>,
+// del2uv_body<HO>; rstar.h), and step n+1 starts at k_dt_l2.  No block reads a location another
+// block of the grid writes.  Longest body first:
+//   [CALC_PHI_HYD(n+1) column frame | CALC_R_STAR + UPDATE_ETAH | blocking exchanges | del2uv(n+1)]
+__global__ void __launch_bounds__(256) k_rstar_exch_phi(Dims d, Params p, Fields f, const long *__restrict__ srcOf, int nbR,
+                                                        XFields x, const long *__restrict__ map, int nHalo, int *ctr,
+                                                        int nbX, int nzMax, int nbXall, int fromX, int empNext, int nc,
+                                                        int nbPhi) {
+  int lb = mg_xcd_block();
+  if (lb < nbPhi) { phi_hyd_body<false, true>(d, p, f, nc, lb, nullptr, srcOf, fromX); return; }
+  lb -= nbPhi;
+  if (lb < nbR) { calc_r_star_body<true>(d, p, f, srcOf, lb, fromX, empNext); return; }
+  lb -= nbR;
+  if (lb < nbXall) { exchange_multi_body(d, x, map, nHalo, ctr, lb % nbX, (lb / nbX) % nzMax, lb / (nbX * nzMax)); return; }
+  del2uv_body<true>(d, p, f, lb - nbXall, srcOf);
+}
+
+// where the rider is exact and has its column frame: r* with the column-frame CALC_PHI_HYD in the
+// default layout's first grid (not the flat pass), and MGCM_STEP_FUSE bit MG_FUSE_PHIP
+bool phi_pipe_ok(const Dims &d, const Params &p) {
+  (void)d;
+  return mg_fuse_on(MG_FUSE_PHIP) && p.nonlinFreeSurf > 0 && p.select_rStar > 0 && p.exactConserv && !p.cubeCorners &&
+         dyn_thermo_takes_gm(p) && !phi_flat_on(p);
+}
+
+// CALC_PHI_HYD | del2uv stand-alone, for the first step of a pipelined call (k_dt_l1 without the tensor)
+hipError_t launch_phi_del2(const Dims &d, const Params &p, const Fields &f, hipStream_t s) {
+  launch_l1(d, p, f, del2_needed(p) ? (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr) : 0, s, 0, false);
+  return hipGetLastError();
+}
+
+// launch_rstar_exch (kernels_rstar.hip) with the next step's CALC_PHI_HYD and del2uv; x is the
+// exchange set without totPhiHyd
+hipError_t launch_rstar_exch_phi(const Dims &d, const Params &p, const Fields &f, const long *srcOf, const XFields &x,
+                                 const long *map, int nHalo, int *ctr, hipStream_t s, int fromX, int empNext) {
+  if (!phi_pipe_ok(d, p) || !srcOf || d.nT != d.nTiles) return hipErrorInvalidValue;
+  const long n = d.n2 * d.nTiles;
+  const int nbR = (int)((n + 255) / 256);
+  int nzMax = 1;
+  for (int q = 0; q < x.n; q++) nzMax = x.nz[q] > nzMax ? x.nz[q] : nzMax;
+  const int nbX = ((nHalo > 0 ? nHalo : 1) + 255) / 256;
+  const int nbXall = nbX * nzMax * (x.n > 0 ? x.n : 1);
+  int nc, nArr, nbPhi;
+  phi_frame(d, p, nc, nArr, nbPhi);
+  const int nbDel = del2_needed(p) ? (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr) : 0;
+  MG_ALLOW_LDS(k_rstar_exch_phi);
+  hipLaunchKernelGGL(k_rstar_exch_phi, dim3((unsigned)(nbPhi + nbR + nbXall + nbDel)), dim3(256), mg_colf_lds(d.Nr, nc, nArr),
+                     s, d, p, f, srcOf, nbR, x, map, nHalo, ctr, nbX, nzMax, nbXall, fromX, empNext, nc, nbPhi);
+  return hipGetLastError();
 }
 
 }  // namespace mgcm

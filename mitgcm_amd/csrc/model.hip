@@ -82,7 +82,8 @@ hipError_t launch_rstar_exmix(const Dims &, const Params &, const Fields &, cons
 hipError_t launch_rstar_exch(const Dims &, const Params &, const Fields &, const long *, bool, const XFields &, const long *,
                              int, int *, hipStream_t, int fromX = 0, int empNext = 0);
 hipError_t launch_update_r_star_cg2d(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool sfp = false,
-                                     bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr);
+                                     bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr,
+                                     bool keepFac = false);
 hipError_t launch_halo_pack(const Dims &, const XFields &, const long *, long, double *, int, hipStream_t);
 hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
                                bool *ringDone = nullptr);
@@ -90,7 +91,11 @@ hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, cons
                               bool impl = true);
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
 hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
-                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true);
+                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true);
+bool phi_pipe_ok(const Dims &, const Params &);
+hipError_t launch_phi_del2(const Dims &, const Params &, const Fields &, hipStream_t);
+hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, const long *, const XFields &, const long *, int,
+                                 int *, hipStream_t, int fromX, int empNext);
 bool dyn_thermo_takes_gm(const Params &);
 hipError_t launch_gm_tensor(const Dims &, const Params &, const Fields &, hipStream_t);
 hipError_t launch_hfac_snapshot(const Dims &, const Fields &, double *, hipStream_t);
@@ -1383,8 +1388,9 @@ static hipError_t calc_r_star(mgcm_model *m, bool fuseEtaH = false, int fromX = 
 // sfp: k_sfp_rhs fused into the r* column pass (FORWARD_STEP on the whole domain only: in a
 // tile-sharded run the r* pass covers every tile and the right-hand side this process's own)
 static hipError_t update_r_star_cg2d(mgcm_model *m, bool sfp = false, bool opEarly = false, bool pcHere = false,
-                                     const int *physNext = nullptr) {
-  return launch_update_r_star_cg2d(all_tiles(m->d), m->p, m->f, m->d_srcOf, m->stream, sfp, opEarly, pcHere, physNext);
+                                     const int *physNext = nullptr, bool keepFac = false) {
+  return launch_update_r_star_cg2d(all_tiles(m->d), m->p, m->f, m->d_srcOf, m->stream, sfp, opEarly, pcHere, physNext,
+                                   keepFac);
 }
 
 int mgcm_init(mgcm_model *m) {
@@ -1716,7 +1722,7 @@ int mgcm_calc_r_star(mgcm_model *m) {
   return 0;
 }
 
-static XFields blocking_fields(const mgcm_model *m, int tracers = 1);
+static XFields blocking_fields(const mgcm_model *m, int tracers = 1, bool totPhi = true);
 
 int mgcm_blocking_exchanges(mgcm_model *m) {
   if (check_ready(m)) return -1;
@@ -1812,14 +1818,16 @@ long mgcm_field_count(mgcm_model *m, const char *name) {
 
 // tracers: 1 every field (the reference's set), 0 without theta/salt (exchanged beside the
 // pressure solve, one_step), 2 theta/salt only
-static XFields blocking_fields(const mgcm_model *m, int tracers) {
+// totPhi = false: without totPhiHyd (a step whose last grid runs the next step's CALC_PHI_HYD, which
+// stores totPhiHyd on exchange destinations; its halo is next read at the sources, one_step)
+static XFields blocking_fields(const mgcm_model *m, int tracers, bool totPhi) {
   XFields x{};
   // do_fields_blocking_exchanges.F:54-97 (+ EXCH_UV_DGRID of uVelD/vVelD with the CD scheme,
   // totPhiHyd when the EOS reads it)
   // (on an EXCH2 topology u, v go through the vector map instead: exchange_uv)
   double *fl[] = {m->f.uVel, m->f.vVel, m->f.wVel, m->f.theta, m->f.salt, m->f.uVelD, m->f.vVelD, m->f.totPhiHyd};
   const bool use[] = {!m->uvMap, !m->uvMap, true, m->p.tempStepping != 0, m->p.saltStepping != 0, m->p.useCDscheme != 0,
-                      m->p.useCDscheme != 0, m->p.storePhiHyd4Phys != 0};
+                      m->p.useCDscheme != 0, m->p.storePhiHyd4Phys != 0 && totPhi};
   for (int q = 0; q < 8; q++) {
     const bool tr = q == 3 || q == 4;
     if (use[q] && (tracers == 1 || (tracers == 2) == tr)) { x.p[x.n] = fl[q]; x.nz[x.n] = m->d.Nr; x.n++; }
@@ -1840,13 +1848,21 @@ static XFields blocking_fields(const mgcm_model *m, int tracers) {
 // fold's first grid without the tensor's blocks.  mgcm_forward_step runs the two stand-alone
 // for the first step of a call (so a put between calls is honoured) and leaves the last step
 // without the riders, so after a call every field holds what the plain steps leave.
+//
+// With MG_FUSE_PHIP (step_phi_pipelinable) the next step's CALC_PHI_HYD and del2uv -- the first
+// of DYNAMICS' grids, which from the step before needs only its last launch's halos of u, v and
+// r* factors -- run in that last launch too (kernels_step.hip k_rstar_exch_phi), and the step
+// starts at the momentum grid: six launches.  The head of a call then runs that grid stand-alone
+// as well, after DO_OCEANIC_PHYS + tensor, from the halos as the caller left them.
 enum StepMode {
   STEP_PLAIN = 0,   // the step runs its own DO_OCEANIC_PHYS + tensor
   STEP_HOIST = 1,   // its own are already done; it runs the next step's
   STEP_LAST = 2     // its own are already done; it runs nobody's (the last step of a call)
 };
 // a call of fewer steps keeps the plain step: the stand-alone head of a pipelined call costs
-// two launches, each hoisting step saves one (profiles/r07/step_pipeline/threshold.md)
+// two launches, each hoisting step saves one (profiles/r07/step_pipeline/threshold.md); with
+// MG_FUSE_PHIP three launches, and every step saves two: the same threshold, a call of 3 gains
+// less than three times what two processes differ by (profiles/r08/step_pipeline_phi/threshold.md)
 #define MG_PIPE_MIN_STEPS 4
 // where the substitutions of the hoisted pass are exact (phys.h) and its host grids run
 static bool step_pipelinable(mgcm_model *m) {
@@ -1865,9 +1881,15 @@ static bool step_pipelinable(mgcm_model *m) {
   if (p.eosType == 1 && p.selectP_inEOS_Zc == 2 && !p.storePhiHyd4Phys) return false;
   return true;
 }
+// ... and where CALC_PHI_HYD and del2uv of the next step ride in the step's last grid as well
+static bool step_phi_pipelinable(mgcm_model *m) {
+  return step_pipelinable(m) && phi_pipe_ok(m->d, m->p);
+}
 static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   const bool pipe = mode != STEP_PLAIN, hoist = mode == STEP_HOIST;
   if (pipe && !step_pipelinable(m)) return set_err("one_step: the pipelined step does not apply to this model");
+  // (its own CALC_PHI_HYD + del2uv are already done; a hoisting step runs the next step's)
+  const bool phiPipe = pipe && step_phi_pipelinable(m);
   // THERMODYNAMICS reads u, v, w, hFac and DO_OCEANIC_PHYS's outputs and writes only the
   // tracers' other buffers and AB histories; DYNAMICS reads none of those.  So once
   // DO_OCEANIC_PHYS is done the two run concurrently (second stream), joined before
@@ -1948,7 +1970,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   const bool physPhi = !stagger && m->p.momStepping && phys_phi_fusable(m->d, m->p);
   // (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
   m->stepLayout = (dtFused ? 1 : 0) | (physPhi ? 2 : 0) | (forkable && !dtFused ? 4 : 0) |
-                  ((forkable && m->p.nonlinFreeSurf <= 0) || tcg ? 8 : 0) | (pipe ? 16 : 0);
+                  ((forkable && m->p.nonlinFreeSurf <= 0) || tcg ? 8 : 0) | (pipe ? 16 : 0) | (phiPipe ? 32 : 0);
   // GMREDI_CALC_TENSOR beside CALC_PHI_HYD (launch_gm_phi) where THERMODYNAMICS, its reader,
   // runs after DYNAMICS (staggered, or forked after CALC_DIV_GHAT) and the fold does not apply
   const bool gmPhi = (stagger || thermoLate) && !dtFused && !physPhi && !m->timing && gm_phi_fusable(m->d, m->p);
@@ -1983,7 +2005,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   if (m->p.momStepping) {
     if (dtFused) {
       TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, aT, aS, m->d_ctr, m->stream, opEarly ? m->d_srcOf : nullptr,
-                                     !pipe));
+                                     !pipe, !phiPipe));
       std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new tracers are the other buffers
       std::swap(m->f.salt, m->f.saltNext);
     } else if (physPhi) TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, !ringAside && !ringPhys));
@@ -2000,7 +2022,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
     // walking every 2-D point costs more than the launch it saves)
     const bool sfpFused = mg_fuse_on(MG_FUSE_SFP) && m->p.nonlinFreeSurf > 0 && m->d.nT == m->d.nTiles;
     if (m->p.nonlinFreeSurf > 0)
-      TIMED(K_RSTAR, update_r_star_cg2d(m, sfpFused, opEarly, false, hoist ? m->d_ctr : nullptr));
+      TIMED(K_RSTAR, update_r_star_cg2d(m, sfpFused, opEarly, false, hoist ? m->d_ctr : nullptr, hoist && phiPipe));
     if (!sfpFused) TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
     // the late fork: THERMODYNAMICS beside the CG2D only, CALC_DIV_GHAT (an HBM stream, on the
     // critical path) alone before it -- LLC-90 1.528-1.532 -> 1.474-1.476 ms/step, alternating
@@ -2045,7 +2067,11 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
     // (k_rstar_exch; independent, and nothing between them in the non-staggered step)
     endFused = m->p.nonlinFreeSurf > 0 && !stagger && !m->uvMap && m->d.nT == m->d.nTiles &&
                mg_hfuse(MG_FUSE_END, m->d.nx, m->d.ny, m->d.nT, m->d.Nr);
-    if (endFused)
+    if (endFused && hoist && phiPipe) {
+      if (!fuseEtaH) return set_err("one_step: the hoisted CALC_PHI_HYD needs UPDATE_ETAH in CALC_R_STAR's pass");
+      TIMED(K_RSTAR, launch_rstar_exch_phi(m->d, m->p, m->f, m->d_srcOf, blocking_fields(m, 1, false), m->d_halo, m->nHalo,
+                                           m->d_ctr, m->stream, etaX ? 1 : 0, m->p.periodicExternalForcing ? 1 : 0));
+    } else if (endFused)
       TIMED(K_RSTAR, launch_rstar_exch(m->d, m->p, m->f, m->d_srcOf, fuseEtaH, blocking_fields(m), m->d_halo, m->nHalo,
                                        m->d_ctr, m->stream, etaX ? 1 : 0,
                                        hoist && m->p.periodicExternalForcing ? 1 : 0));
@@ -2257,6 +2283,10 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
   // runs the next step's, and the last leaves every field as the plain step does
   const bool pipe = nsteps >= MG_PIPE_MIN_STEPS && step_pipelinable(m);
   if (pipe) TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream));
+  // ... and, where every step's CALC_PHI_HYD + del2uv run in the step before (MG_FUSE_PHIP), the
+  // first step's: from the halos of u and v as the caller left them
+  const bool phiPipe = pipe && step_phi_pipelinable(m);
+  if (phiPipe) TIMED(K_PHI, launch_phi_del2(m->d, m->p, m->f, m->stream));
   if (m->useGraph && !m->timing) {
     for (; s + 2 <= nsteps; s += 2) {
       hipGraphExec_t ge;
@@ -2275,7 +2305,8 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
   }
   for (; s < nsteps; s++)
     if (one_step(m, pipe ? (s == nsteps - 1 ? STEP_LAST : STEP_HOIST) : STEP_PLAIN)) return -1;
-  m->stepLayout = (m->stepLayout & ~16) | (pipe ? 16 : 0);   // (the layout this call ran, whichever graph was built last)
+  // (the layout this call ran, whichever graph was built last)
+  m->stepLayout = (m->stepLayout & ~48) | (pipe ? 16 : 0) | (phiPipe ? 32 : 0);
   m->lastBatch = nsteps;
   return 0;
 }

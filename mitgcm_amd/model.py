@@ -26,6 +26,8 @@ STATE_1D = ("tRef", "sRef", "pRef4EOS", "phiRefC")
 STATE_3D = ("uVel", "vVel", "wVel", "theta", "salt", "gU", "gV", "guNm1", "gvNm1", "gtNm1", "gsNm1", "rhoInSitu",
             "IVDConvCount", "sigmaR", "Kwx", "Kwy", "Kwz", "Kux", "Kvy", "uVelD", "vVelD", "uNM1", "vNM1",
             "totPhiHyd", "alphaRho", "del2u", "del2v", "Kuz", "Kvz", "GM_PsiX", "GM_PsiY")
+# 3-D work fields of DYNAMICS a get() may read (CALC_PHI_HYD's phi and MOM_CALC_RTRANS's dWtrans)
+WORK_3D = ("phiHydC", "dWtC", "dWtU", "dWtV")
 STATE_2D = ("etaN", "etaH", "fu", "fv", "SST", "lambdaThetaClimRelax", "surfaceForcingT", "surfaceForcingS",
             "Qnet", "EmPmR", "SSS", "lambdaSaltClimRelax", "etaNm1", "rStarFacC", "rStarFacW", "rStarFacS",
             "rStarExpC", "rStarExpW", "rStarExpS", "rStarDhCDt", "rStarDhWDt", "rStarDhSDt", "PmEpR", "dEtaHdt")
@@ -104,7 +106,7 @@ class Model:
         g = self.g
         if name in GRID_1D or name in STATE_1D:
             return (g.Nr + 1,)
-        if name in GRID_3D or name in STATE_3D:
+        if name in GRID_3D or name in STATE_3D or name in WORK_3D:
             return (g.nTiles, g.Nr, g.ny, g.nx)
         if name == "forcRec":   # 6 forcing fields x the device's record capacity, 2-D each
             n = lib().mgcm_field_count(self.h, b"forcRec")
@@ -214,10 +216,12 @@ class Model:
         """The launch layout of the last step built (mgcm_get_param 'stepLayout'): which
         fusions of one_step (model.hip) the timed graph and the eager timed pass run.
         'pipelined': the last forward_step call ran the next step's DO_OCEANIC_PHYS and
-        GMREDI_CALC_TENSOR inside each step (MGCM_STEP_FUSE bit 16384; calls of 4 steps or more)."""
+        GMREDI_CALC_TENSOR inside each step (MGCM_STEP_FUSE bit 16384; calls of 4 steps or more).
+        'phi_pipelined': it also ran the next step's CALC_PHI_HYD and del2uv in each step's last
+        grid (bit 32768, with 'pipelined')."""
         b = int(lib().mgcm_get_param(self.h, b"stepLayout"))
         return {"dyn_thermo_fused": bool(b & 1), "phys_phi_fused": bool(b & 2), "thermo_second_stream": bool(b & 4),
-                "late_join": bool(b & 8), "pipelined": bool(b & 16)}
+                "late_join": bool(b & 8), "pipelined": bool(b & 16), "phi_pipelined": bool(b & 32)}
 
     def cg2d_fma(self):
         """True when the selected CG2D kernel solves in fused multiply-adds (cg2dUseFMA): the
