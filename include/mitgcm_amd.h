@@ -71,6 +71,25 @@ int mgcm_add_iter(mgcm_model *m, int inc);
  * the current parity; set = 0..3 makes that parity current (a replayed step whose capture
  * already ran the host-side swaps: fortran_abi.hip). */
 int mgcm_tracer_parity(mgcm_model *m, int set);
+/* With passive tracers bit 2 is theirs: all of them swap buffers together, once per step;
+ * set = 0..7 then. */
+
+/* pkg/ptracers: n = 1..99 passive tracers, each stepped through SALT_INTEGRATE's sequence with
+ * its own parameters (pkg/ptracers/ptracers_integrate.F).  Call before mgcm_init; allocates
+ * the tracers' ping-pong pairs, AB2 histories and scratch.  Their fields are "pTracer01".."pTracer99"
+ * and "gpTrNm1_01".."gpTrNm1_99" for mgcm_put / mgcm_get / mgcm_field_count / mgcm_device_ptr.
+ * Without this call nothing of the model changes. */
+int mgcm_ptracers_alloc(mgcm_model *m, int n);
+/* Parameters of tracer iTracer (1-based): advScheme (vertical = horizontal), diffKh, diffKr,
+ * useGMRedi (default: the model's), and the forcing restated from the reference's
+ * experiment code: surfRelaxTau, surfRelaxVal (surface relaxation,
+ * surfaceForcingPTr = (1/tau)*(val - pTracer(k=1))*drF(1)*hFacC(k=1); tau = 0: none) and
+ * interiorSource (added times maskC at every k != 1).  EvPrRn (PTRACERS_EvPrRn) is refused
+ * by mgcm_init: only the unset case is built. */
+int mgcm_ptracer_param(mgcm_model *m, int iTracer, const char *name, double value);
+double mgcm_ptracer_param_get(mgcm_model *m, int iTracer, const char *name);
+/* Number of passive tracers allocated (0: none). */
+int mgcm_ptracers_count(mgcm_model *m);
 
 /* Host <-> device copies of named fields (DYNVARS/GRID/CG2D/FFIELDS names,
  * e.g. "uVel", "hFacW", "aW2d", "fu").  count = number of doubles. */

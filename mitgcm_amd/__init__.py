@@ -6,5 +6,5 @@ with a host driver mirroring the reference's FORWARD_STEP sequence.
 """
 from ._lib import MgcmError, lib  # noqa: F401
 from .grid import Grid  # noqa: F401
-from .model import Model, dynstat  # noqa: F401
+from .model import Model, dynstat, trcstat  # noqa: F401
 from .topology import LatLonTopology  # noqa: F401

@@ -35,6 +35,10 @@ def lib():
         "mgcm_add_iter": (ci, [vp, ci]),
         "mgcm_exch2_maps": (ci, [ci] * 6 + [PI] * 16 + [ci] + [PL] * 5),
         "mgcm_tracer_parity": (ci, [vp, ci]),
+        "mgcm_ptracers_alloc": (ci, [vp, ci]),
+        "mgcm_ptracers_count": (ci, [vp]),
+        "mgcm_ptracer_param": (ci, [vp, ci, cs, cd]),
+        "mgcm_ptracer_param_get": (cd, [vp, ci, cs]),
         "mgcm_get_param": (cd, [vp, cs]),
         "mgcm_put": (ci, [vp, cs, PD, cl]),
         "mgcm_put_async": (ci, [vp, cs, PD, cl]),
@@ -119,7 +123,8 @@ EXPORTS = ["mgcm_create", "mgcm_destroy", "mgcm_last_error", "mgcm_set_param", "
            "mgcm_set_iter", "mgcm_add_iter", "mgcm_tracer_parity", "mgcm_exch2_maps", "mgcm_amd_host_sync_", "mgcm_amd_device_sync_", "mgcm_amd_transfer_stats_",
            "mgcm_amd_step_fence_", "mgcm_halo_pack_group", "mgcm_exchange_nfields_group", "mgcm_stream_handoff",
            "mgcm_end_steps", "mgcm_cg2d_shared_bytes", "mgcm_cg2d_shared_export", "mgcm_cg2d_shared_import",
-           "mgcm_amd_set_maps_", "mgcm_amd_set_w2_", "mgcm_get_stream", "mgcm_halo_sources", "mgcm_cg2d_tiles", "mgcm_cg2d_share"]
+           "mgcm_amd_set_maps_", "mgcm_amd_set_w2_", "mgcm_get_stream", "mgcm_halo_sources", "mgcm_cg2d_tiles", "mgcm_cg2d_share",
+           "mgcm_ptracers_alloc", "mgcm_ptracers_count", "mgcm_ptracer_param", "mgcm_ptracer_param_get"]
 
 
 def check(rc, what):

@@ -161,10 +161,12 @@ def advect_xy(nSx=1, nSy=2):
     return g, params, state
 
 
-def make_model(cfg, device=0, **kw):
+def make_model(cfg, device=0, ptracers=None, **kw):
+    """ptracers: a list of passive-tracer parameter dicts (Model.add_ptracers), e.g.
+    global_oce_latlon_ptracers()."""
     out = cfg(**kw)
     g, params, state = out[:3]
-    m = Model(g, params, device=device)
+    m = Model(g, params, device=device, ptracers=ptracers)
     for k, v in state.items():
         m.put(k, v)
     if len(out) > 3:
@@ -254,6 +256,17 @@ def global_oce_latlon(nSx=2, nSy=1, OL=2, data_dir=None):
              "fu": forcing["taux"][0], "fv": forcing["tauy"][0], "Qnet": forcing["Qnet"][0],
              "EmPmR": forcing["EmPmR"][0], "SST": forcing["SST"][0], "SSS": forcing["SSS"][0]}
     return g, params, state, forcing
+
+
+def global_oce_latlon_ptracers():
+    """The passive tracer of verification/tutorial_global_oce_latlon (input/data.ptracers:
+    PTRACERS_numInUse=1, advScheme=33, diffKh=0, diffKr=3e-5, no initial file: zero): an age
+    tracer, relaxed to 0 in the surface level over 10 days (code/ptracers_forcing_surf.F) and
+    growing by 1 per second below it (code/ptracers_apply_forcing.F); data.ptracers leaves
+    PTRACERS_useGMRedi and PTRACERS_ImplVertAdv at the model's (GM/Redi on, implicit diffusion).
+    For make_model(global_oce_latlon, ptracers=...)."""
+    return [dict(name="Age_tracer", advScheme=33, diffKh=0.0, diffKr=3e-5, surfRelaxTau=864000.0, surfRelaxVal=0.0,
+                 interiorSource=1.0, init=0.0)]
 
 
 PICKUP_FIELDS = ("uVel", "vVel", "theta", "salt", "guNm1", "gvNm1", "gtNm1", "gsNm1", "totPhiHyd")

@@ -345,7 +345,28 @@ struct TracerArgs {
   int limiter;          // multi-dim face fluxes: 1 DST3FL (scheme 33), 0 DST3 (scheme 30)
   int scheme;           // the advection scheme (2 C2, 3 U3, 4 C4 inside GAD_CALC_RHS; 30/33 multi-dim)
   double *gNm2;         // ADAMS_BASHFORTH3: gtNm(:,:,:,2) (gNm1 is slot 1)
+  // passive tracers (pkg/ptracers; all "off" for theta and salt, whose arithmetic they leave alone)
+  double relaxRate;     // 1/surfRelaxTau, 0: no surface relaxation (ptracers_forcing_surf.F)
+  double relaxVal;      // the value the surface level is relaxed to
+  double src;           // interior source at every k != 1 (ptracers_apply_forcing.F), 0: none
+  int gm;               // the tracer's useGMRedi (PTRACERS_useGMRedi): both passive-tracer routes step the
+                        // tracer with Params.useGMRedi set to it (ptracers_on, k_ptr_rhs, k_ptr_impl)
+  // the tracer's own multi-dimensional advection scratch (null: the model's advScr1 / advScr2 / gAdv)
+  double *adv1, *adv2, *gAdv;
 };
+// The Fields a passive tracer's kernels get: its own multi-dimensional scratch in place of the
+// model's (the bodies reach advScr1 / advScr2 / gAdv through these pointers only); both routes
+__host__ __device__ inline Fields ptr_fields(const Fields &f, const TracerArgs &a) {
+  Fields g = f;
+  g.advScr1 = a.adv1; g.advScr2 = a.adv2; g.gAdv = a.gAdv;
+  return g;
+}
+// surfaceForcingPTr of a tracer with surface relaxation (ptracers_forcing_surf.F, the
+// experiment's own code/ form restated with parameters): evaluated left to right from the
+// tracer at the start of the step
+__device__ __forceinline__ double ptr_surf_relax(const TracerArgs &a, double trSurf, double drF1, double hFacC1) {
+  return (((a.relaxRate * (a.relaxVal - trSurf)) * drF1) * hFacC1);
+}
 
 // Fields exchanged together by k_exchange_multi.
 #define MG_XMAX 8

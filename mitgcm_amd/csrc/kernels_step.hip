@@ -367,3 +367,6 @@ hipError_t launch_rstar_exch_phi(const Dims &d, const Params &p, const Fields &f
 }
 
 }  // namespace mgcm
+
+// pkg/ptracers: the batched passive-tracer kernels (they run kernels_thermo.hip's bodies)
+#include "kernels_ptracers.hip"

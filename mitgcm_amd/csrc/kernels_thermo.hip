@@ -111,8 +111,10 @@ __device__ __forceinline__ double dst3fl_h(double uTr, double cfl, double tm2, d
 // GAD_ADVECTION (gad_advection.F), lat-lon operator splitting (npass = 2), X pass:
 // loc1 = T - dT/(h drF rA) * (afx(i+1) - afx(i) - T*(uTrans(i+1) - uTrans(i))) * maskInC
 // on i = 2-OLx..sNx+OLx-1, every j; elsewhere loc1 = T.
-__global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) {
-  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
+// (the three passes as device functions of a logical block id: k_adv_x/y/r run them for one
+// tracer, the batched passive-tracer kernels for several, kernels_ptracers.hip)
+__device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const TracerArgs &a, int lb) {
+  MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
   const double *__restrict__ T = a.tr;
@@ -134,11 +136,12 @@ __global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) {
   }
   f.advScr1[q3] = v;
 }
+__global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) { adv_x_body(d, f, a, mg_xcd_block()); }
 
 // Y pass on the interior (the only rows the vertical pass and the tendency use):
 // loc2 = loc1 - dT/(h drF rA) * (afy(j+1) - afy(j) - T*(vTrans(j+1) - vTrans(j))) * maskInC
-__global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) {
-  MG_PLANE(1, d.sNx, 1, d.sNy, z)
+__device__ __forceinline__ void adv_y_body(const Dims &d, const Fields &f, const TracerArgs &a, int lb) {
+  MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx || j > d.sNy) return;
   const double *__restrict__ L1 = f.advScr1;
@@ -156,14 +159,15 @@ __global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) {
   f.advScr2[q3] = L1[q3] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
                                (afy(j + 1) - afy(j) - a.tr[q3] * (vTr(j + 1) - vTr(j))) * f.maskInC[q];
 }
+__global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) { adv_y_body(d, f, a, mg_xcd_block()); }
 
 // vertical pass + advective tendency (gad_advection.F k = Nr..1 loop) on the horizontally
 // advected tracer L (and, GAD_MULTIDIM_COMPRESSIBLE, the local volume V, :1036-1057):
 // gAdv = (loc - T)/dT, or (tmpTrac - T*vol)/(rA drF hFac dT) in the compressible form
 template <bool COMP>
-__global__ void __launch_bounds__(256) k_adv_r(Dims d, Params p, Fields f, TracerArgs a, const double *__restrict__ L2,
-                                               const double *__restrict__ V) {
-  MG_PLANE(1, d.sNx, 1, d.sNy, z)
+__device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a,
+                                           const double *__restrict__ L2, const double *__restrict__ V, int lb) {
+  MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx || j > d.sNy) return;
   const int Nr = d.Nr;
@@ -202,6 +206,11 @@ __global__ void __launch_bounds__(256) k_adv_r(Dims d, Params p, Fields f, Trace
   }
 #undef MC
 #undef LT
+}
+template <bool COMP>
+__global__ void __launch_bounds__(256) k_adv_r(Dims d, Params p, Fields f, TracerArgs a, const double *__restrict__ L2,
+                                               const double *__restrict__ V) {
+  adv_r_body<COMP>(d, p, f, a, L2, V, mg_xcd_block());
 }
 
 // ---------------------------------------------------------------------------
@@ -566,7 +575,10 @@ __device__ __forceinline__ double gad_u3c4_r(bool c4, int k, int Nr, double rTr,
   }
   return mkm1 * (rTr * ((tk + tkm1) * 0.5 - oneSixth * (Rjjm + Rjjp) * 0.5) + fabs(rTr) * oneSixth * (Rjjm - Rjjp) * 0.5);
 }
-template <bool GM>
+// PTR: a passive tracer's forcing (pkg/ptracers): surfaceForcingPTr from the surface relaxation
+// instead of a.sfc (ptracers_forcing_surf.F) and the interior source at k != 1
+// (ptracers_apply_forcing.F); theta and salt never instantiate it
+template <bool GM, bool PTR = false>
 __device__ __forceinline__ void tracer_rhs_body(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a,
                                                 const int *iterPtr, int lb) {
   MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
@@ -742,6 +754,11 @@ __device__ __forceinline__ void tracer_rhs_body(const Dims &d, const Params &p, 
                         Tk * ((uT1 - uT0) * advFac + (vT1 - vT0) * advFac + (rTransKp - rTrans) * rAdvFac) * maskInC);
   double gtForc = 0.0;
   if (a.forcing && a.sfc && k == 1) gtForc = gtForc + a.sfc[q] * f.recip_drF[0] * f.recip_hFacC[q3];
+  if constexpr (PTR) {
+    if (a.relaxRate != 0.0 && k == 1)
+      gtForc = gtForc + ptr_surf_relax(a, Tk, f.drF[0], f.hFacC[q3]) * f.recip_drF[0] * f.recip_hFacC[q3];
+    if (a.src != 0.0 && k != 1) gtForc = gtForc + a.src * G3(maskC, i, j, k);
+  }
   if (!p.tracForcingOutAB) gT = gT + gtForc;   // inside (0) / after (1) AB2: temp_integrate.F:373-410
   if (a.useAB && p.useAB3) {   // ADAMS_BASHFORTH3(k) (adams_bashforth3.F:60-103; startAB = nIter0)
     const int n0 = p.nIter0, startAB = p.nIter0;
@@ -773,9 +790,9 @@ __device__ __forceinline__ void tracer_rhs_body(const Dims &d, const Params &p, 
 #undef G2
 #undef G3
 }
-template <bool GM>
+template <bool GM, bool PTR = false>
 __global__ void __launch_bounds__(256) k_tracer_rhs(Dims d, Params p, Fields f, TracerArgs a, const int *iterPtr) {
-  tracer_rhs_body<GM>(d, p, f, a, iterPtr, mg_xcd_block());
+  tracer_rhs_body<GM, PTR>(d, p, f, a, iterPtr, mg_xcd_block());
 }
 
 // k_tracer_rhs without GM/Redi, every load issued up front: the same expression trees as
@@ -1334,7 +1351,12 @@ hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, c
     }
   }
   // GM/Redi fluxes as a template switch: without them the kernel holds half the registers
-  if (p.useGMRedi) hipLaunchKernelGGL(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
+  // a passive tracer with forcing of its own (pkg/ptracers): the generic body's PTR form, whose
+  // arithmetic is the flat and marching forms' (they are bit-identical restatements of it)
+  const bool ptrForc = a.relaxRate != 0.0 || a.src != 0.0;
+  if (ptrForc && p.useGMRedi) hipLaunchKernelGGL((k_tracer_rhs<true, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
+  else if (ptrForc) hipLaunchKernelGGL((k_tracer_rhs<false, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
+  else if (p.useGMRedi) hipLaunchKernelGGL(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (a.scheme != 2 || p.useAB3)   // U3 / C4 and ADAMS_BASHFORTH3: the generic body only
     hipLaunchKernelGGL(k_tracer_rhs<false>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (tracer_march_on(d)) {

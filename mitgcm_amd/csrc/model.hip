@@ -106,6 +106,9 @@ bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const Tra
 hipError_t launch_tracer_hpair(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &,
                                const int *, hipStream_t);
 hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, hipStream_t);
+bool ptr_batch_ok(const Dims &, const Params &);
+hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int, int, int,
+                                 int, const int *, hipStream_t);
 }  // namespace mgcm
 
 using namespace mgcm;
@@ -270,16 +273,33 @@ struct mgcm_model {
   // hipGraphs of two FORWARD_STEPs, one per theta/salt ping-pong parity
   bool useGraph = true;
   // [THERMODYNAMICS overlap off/on][tracer buffer parity][step modes: 0 plain, plain; 1 hoist, hoist; 2 hoist, last]
-  hipGraphExec_t graphExec[2][4][3] = {};
+  // (parity: bit 0 theta, 1 salt, 2 the passive tracers)
+  hipGraphExec_t graphExec[2][8][3] = {};
   // ONE step (callers that step one at a time: the Fortran drop-ins) [..][..][step mode: 0 plain, 1 last]
-  hipGraphExec_t graph1Exec[2][4][2] = {};
-  double *graph1Tr[2][4][2][4] = {};     // its tracer pointers after the step: theta, thetaNext, salt, saltNext
+  hipGraphExec_t graph1Exec[2][8][2] = {};
+  double *graph1Tr[2][8][2][4] = {};     // its tracer pointers after the step: theta, thetaNext, salt, saltNext
+  bool graph1Flip[2][8][2] = {};         // ... and the passive tracers' parity after it
   // overlap auto-selection (ovl_trial): both graphs timed on a copy of the state
   bool ovlAuto = false, ovlDecided = false;
   float ovlMs[2] = {0.f, 0.f};
   hipEvent_t ovlEv[2] = {nullptr, nullptr};
   double *thetaA = nullptr, *saltA = nullptr;
   int stepLayout = 0;   // one_step's launch layout (mgcm_get_param "stepLayout")
+  // pkg/ptracers (mgcm_ptracers_alloc): a third arena, sized at run time, of PTR_NF 3-D fields
+  // per tracer -- the ping-pong pair, gpTrNm1 and the tracer's own T*, advScr1 (also the
+  // marches' c'), advScr2 and gAdv scratch: the batched kernels run the tracers concurrently
+  struct PTracer {
+    int advScheme = 2, useGMRedi = -1;   // (-1: the model's useGMRedi)
+    double diffKh = 0.0, diffKr = 0.0, surfRelaxTau = 0.0, surfRelaxVal = 0.0, interiorSource = 0.0, EvPrRn = NAN;
+    double *buf[2] = {nullptr, nullptr}, *gNm1 = nullptr, *scr = nullptr, *adv1 = nullptr, *adv2 = nullptr, *gAdv = nullptr;
+  };
+  std::vector<PTracer> ptr;
+  double *a4 = nullptr;            // the arena
+  int ptrFlip = 0;                 // which buffer of every pair is current (all swap together once per step)
+  TracerArgs *d_ptrTab = nullptr;  // [2 parities][n] the batched kernels' table
+  int *d_ptrList = nullptr;        // [2][n]: the multi-dimensional tracers, then every tracer in launch order
+  int ptrNMd = 0, ptrNGM = 0;       // multi-dimensional tracers; tracers that take GM/Redi (first in launch order)
+  bool ptrTabDirty = true;
   // THERMODYNAMICS of a sharded step on the second stream (mgcm_step_phase 16): 1 forked after
   // DO_OCEANIC_PHYS (joined before UPDATE_R_STAR), 2 to fork after CALC_DIV_GHAT, 3 forked
   // after it (joined before the correction step), 0 none pending
@@ -312,6 +332,7 @@ struct mgcm_model {
 using Cg2dSolver = mgcm_model::Cg2dSolver;
 
 static void drop_graphs(mgcm_model *m);
+static int ptr_tables_sync(mgcm_model *m);
 static int land_eta_check(mgcm_model *m, const char *name, const double *host, long n);
 
 static long field_count(const mgcm_model *m, FieldKind k) {
@@ -327,6 +348,23 @@ static const FieldDesc *find_field(const char *name) {
 }
 static double *&field_ptr(mgcm_model *m, const FieldDesc *fd) {
   return *reinterpret_cast<double **>(reinterpret_cast<char *>(&m->f) + fd->off);
+}
+// A named field's device pointer and size: the Fields members, and the passive tracers'
+// "pTracerNN" (the current buffer) / "gpTrNm1_NN", NN = 01..99 (PTRACERS_SIZE.h's two digits)
+static bool lookup_field(mgcm_model *m, const char *name, double **ptr, long *n) {
+  if (const FieldDesc *fd = find_field(name)) {
+    *ptr = field_ptr(m, fd);
+    *n = field_count(m, fd->kind);
+    return true;
+  }
+  const bool tr = !strncmp(name, "pTracer", 7), g = !strncmp(name, "gpTrNm1_", 8);
+  const char *dg = name + (tr ? 7 : 8);
+  if ((!tr && !g) || dg[0] < '0' || dg[0] > '9' || dg[1] < '0' || dg[1] > '9' || dg[2]) return false;
+  const int i = (dg[0] - '0') * 10 + (dg[1] - '0');
+  if (i < 1 || i > (int)m->ptr.size()) return false;
+  *ptr = tr ? m->ptr[i - 1].buf[m->ptrFlip] : m->ptr[i - 1].gNm1;
+  *n = m->d.n3 * m->d.nTiles;
+  return true;
 }
 
 // ------------------------------------------------------------------ timing
@@ -1085,6 +1123,7 @@ void mgcm_destroy(mgcm_model *m) {
 
 int mgcm_set_param(mgcm_model *m, const char *name, double value) {
   drop_graphs(m);   // kernel arguments are captured by value
+  m->ptrTabDirty = true;   // (the passive tracers' device table holds values derived from the parameters)
   if (!strcmp(name, "myIter")) {  // the device-side iteration counter (AB2 start, solve records)
     int it = (int)value;
     HIPCHK(hipSetDevice(m->device));
@@ -1172,14 +1211,81 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
   return it == m->extra.end() ? NAN : it->second;
 }
 
+// ---- pkg/ptracers: storage and parameters ------------------------------------------------
+#define PTR_NF 7   // 3-D fields per tracer in the arena: the pair, gpTrNm1, T*, advScr1, advScr2, gAdv
+int mgcm_ptracers_alloc(mgcm_model *m, int n) {
+  if (n < 1 || n > 99) return set_err("mgcm_ptracers_alloc: %d tracers outside 1..99 (PTRACERS_num's two digits)", n);
+  if (m->ready) return set_err("mgcm_ptracers_alloc: call before mgcm_init");
+  if (!m->ptr.empty()) return set_err("mgcm_ptracers_alloc: the passive tracers are already allocated (%d)", (int)m->ptr.size());
+  if (m->d.nT != m->d.nTiles)
+    return set_err("mgcm_ptracers_alloc: passive tracers are not supported in tile-sharded runs (tile range [%d, %d) of %d)",
+                   m->d.t0, m->d.t0 + m->d.nT, m->d.nTiles);
+  HIPCHK(hipSetDevice(m->device));
+  const size_t bytes = (size_t)n * PTR_NF * m->d.N3all * sizeof(double);
+  HIPCHK(hipMalloc(&m->a4, bytes));
+  m->allocs.push_back(m->a4);
+  HIPCHK(hipMemset(m->a4, 0, bytes));
+  HIPCHK(hipMalloc(&m->d_ptrTab, 2 * (size_t)n * sizeof(TracerArgs)));
+  m->allocs.push_back(m->d_ptrTab);
+  HIPCHK(hipMalloc(&m->d_ptrList, 2 * (size_t)n * sizeof(int)));
+  m->allocs.push_back(m->d_ptrList);
+  HIPCHK(hipDeviceSynchronize());   // (the zero fill ran on the null stream, as mgcm_create's)
+  m->ptr.assign(n, mgcm_model::PTracer{});
+  for (int i = 0; i < n; i++) {
+    double *b = m->a4 + (size_t)i * PTR_NF * m->d.N3all;
+    mgcm_model::PTracer &t = m->ptr[i];
+    t.buf[0] = b; t.buf[1] = b + m->d.N3all; t.gNm1 = b + 2 * m->d.N3all; t.scr = b + 3 * m->d.N3all;
+    t.adv1 = b + 4 * m->d.N3all; t.adv2 = b + 5 * m->d.N3all; t.gAdv = b + 6 * m->d.N3all;
+  }
+  m->ptrFlip = 0;
+  m->ptrTabDirty = true;
+  drop_graphs(m);
+  return 0;
+}
+int mgcm_ptracers_count(mgcm_model *m) { return (int)m->ptr.size(); }
+
+static double *ptracer_param_slot(mgcm_model::PTracer &t, const char *name, int **ip) {
+  *ip = nullptr;
+  if (!strcmp(name, "advScheme")) { *ip = &t.advScheme; return nullptr; }
+  if (!strcmp(name, "useGMRedi")) { *ip = &t.useGMRedi; return nullptr; }
+  if (!strcmp(name, "diffKh")) return &t.diffKh;
+  if (!strcmp(name, "diffKr")) return &t.diffKr;
+  if (!strcmp(name, "surfRelaxTau")) return &t.surfRelaxTau;
+  if (!strcmp(name, "surfRelaxVal")) return &t.surfRelaxVal;
+  if (!strcmp(name, "interiorSource")) return &t.interiorSource;
+  if (!strcmp(name, "EvPrRn")) return &t.EvPrRn;
+  return nullptr;
+}
+int mgcm_ptracer_param(mgcm_model *m, int iTracer, const char *name, double value) {
+  if (iTracer < 1 || iTracer > (int)m->ptr.size())
+    return set_err("mgcm_ptracer_param: tracer %d outside 1..%d", iTracer, (int)m->ptr.size());
+  int *ip = nullptr;
+  double *dp = ptracer_param_slot(m->ptr[iTracer - 1], name, &ip);
+  if (!dp && !ip) return set_err("mgcm_ptracer_param: unknown parameter %s", name);
+  if (ip) *ip = (int)value;
+  else *dp = value;
+  // (the scheme rules are mgcm_init's: a changed parameter needs a new mgcm_init)
+  if (m->ready && (ip || !strcmp(name, "EvPrRn"))) m->ready = false;
+  m->ptrTabDirty = true;
+  drop_graphs(m);   // kernel arguments are captured by value
+  return 0;
+}
+double mgcm_ptracer_param_get(mgcm_model *m, int iTracer, const char *name) {
+  if (iTracer < 1 || iTracer > (int)m->ptr.size()) return NAN;
+  int *ip = nullptr;
+  double *dp = ptracer_param_slot(m->ptr[iTracer - 1], name, &ip);
+  if (ip) return (double)*ip;
+  return dp ? *dp : NAN;
+}
+
 int mgcm_put(mgcm_model *m, const char *name, const double *host, long count) {
-  const FieldDesc *fd = find_field(name);
-  if (!fd) return set_err("mgcm_put: unknown field %s", name);
-  const long n = field_count(m, fd->kind);
+  double *dev = nullptr;
+  long n = 0;
+  if (!lookup_field(m, name, &dev, &n)) return set_err("mgcm_put: unknown field %s", name);
   if (count > n || count <= 0) return set_err("mgcm_put: %s count %ld > %ld", name, count, n);
   if (m->ready && land_eta_check(m, name, host, count)) return -1;
   HIPCHK(hipSetDevice(m->device));
-  HIPCHK(mg_host_copy(field_ptr(m, fd), host, count * sizeof(double), hipMemcpyHostToDevice, m->stream));
+  HIPCHK(mg_host_copy(dev, host, count * sizeof(double), hipMemcpyHostToDevice, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   return 0;
 }
@@ -1210,13 +1316,11 @@ int mgcm_put_batch_async(mgcm_model *m, int n, const char *const *names, const d
   std::vector<double *> dst(n);
   long total = 0, maxc = 0;
   for (int i = 0; i < n; i++) {
-    const FieldDesc *fd = find_field(names[i]);
-    if (!fd) return set_err("mgcm_put_batch_async: unknown field %s", names[i]);
-    const long lim = field_count(m, fd->kind);
+    long lim = 0;
+    if (!lookup_field(m, names[i], &dst[i], &lim)) return set_err("mgcm_put_batch_async: unknown field %s", names[i]);
     if (counts[i] > lim || counts[i] <= 0)
       return set_err("mgcm_put_batch_async: %s count %ld > %ld", names[i], counts[i], lim);
     if (m->ready && land_eta_check(m, names[i], hosts[i], counts[i])) return -1;
-    dst[i] = field_ptr(m, fd);
     total += counts[i];
     maxc = std::max(maxc, counts[i]);
   }
@@ -1269,20 +1373,21 @@ int mgcm_put_async(mgcm_model *m, const char *name, const double *host, long cou
 }
 
 int mgcm_get(mgcm_model *m, const char *name, double *host, long count) {
-  const FieldDesc *fd = find_field(name);
-  if (!fd) return set_err("mgcm_get: unknown field %s", name);
-  const long n = field_count(m, fd->kind);
+  double *dev = nullptr;
+  long n = 0;
+  if (!lookup_field(m, name, &dev, &n)) return set_err("mgcm_get: unknown field %s", name);
   if (count > n || count <= 0) return set_err("mgcm_get: %s count %ld > %ld", name, count, n);
   HIPCHK(hipSetDevice(m->device));
-  HIPCHK(mg_host_copy(host, field_ptr(m, fd), count * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(mg_host_copy(host, dev, count * sizeof(double), hipMemcpyDeviceToHost, m->stream));
   HIPCHK(hipStreamSynchronize(m->stream));
   return 0;
 }
 
 double *mgcm_device_ptr(mgcm_model *m, const char *name) {
-  const FieldDesc *fd = find_field(name);
-  if (!fd) { set_err("mgcm_device_ptr: unknown field %s", name); return nullptr; }
-  return field_ptr(m, fd);
+  double *dev = nullptr;
+  long n = 0;
+  if (!lookup_field(m, name, &dev, &n)) { set_err("mgcm_device_ptr: unknown field %s", name); return nullptr; }
+  return dev;
 }
 
 int mgcm_set_halo_map(mgcm_model *m, const long *src_of_point, long count) {
@@ -1397,7 +1502,8 @@ int mgcm_init(mgcm_model *m) {
   auto ext = [&](const char *n, double dflt) { auto it = m->extra.find(n); return it == m->extra.end() ? dflt : it->second; };
   HIPCHK(hipSetDevice(m->device));
   // the hFac snapshot THERMODYNAMICS reads beside the pressure solve under r* (one_step)
-  if (!m->snapH && m->p.nonlinFreeSurf > 0 && m->p.select_rStar > 0 && (m->p.tempStepping || m->p.saltStepping)) {
+  if (!m->snapH && m->p.nonlinFreeSurf > 0 && m->p.select_rStar > 0 &&
+      (m->p.tempStepping || m->p.saltStepping || !m->ptr.empty())) {
     HIPCHK(hipMalloc(&m->snapH, 6 * (size_t)m->d.N3all * sizeof(double)));
     m->allocs.push_back(m->snapH);
   }
@@ -1509,6 +1615,29 @@ int mgcm_init(mgcm_model *m) {
     return set_err("mgcm_init: GM_AdvForm with multi-dimensional advection is not implemented on the device");
   if (m->p.useGMRedi && m->p.GM_AdvForm && m->p.GM_skewflx != 0.0)
     return set_err("mgcm_init: GM_AdvForm needs GM_skewflx = 0 (gmredi_readparms.F:243-244)");
+  // pkg/ptracers: a tracer is accepted with exactly the options salt would be accepted with
+  for (size_t it = 0; it < m->ptr.size(); it++) {
+    const mgcm_model::PTracer &t = m->ptr[it];
+    const int s = t.advScheme, no = (int)it + 1;
+    if (!std::isnan(t.EvPrRn))
+      return set_err("mgcm_init: pTracer%02d: PTRACERS_EvPrRn is not implemented on the device (only the unset case: "
+                     "no fresh-water dilution of the tracer)", no);
+    if (m->p.useAB3) return set_err("mgcm_init: passive tracers with ADAMS_BASHFORTH3 (useAB3) are not implemented");
+    if (m->d.nT != m->d.nTiles) return set_err("mgcm_init: passive tracers are not supported in tile-sharded runs");
+    if (wideScheme(s) && (m->uvMap || m->d.OLx < 2 || m->d.OLy < 2))
+      return set_err("mgcm_init: pTracer%02d: advection schemes 3 / 4 need OLx, OLy >= 2 and a lat-lon topology on the device", no);
+    if (m->uvMap && mdScheme(s)) {
+      if (!m->f.tileFace) return set_err("mgcm_init: pTracer%02d: multi-dimensional advection on EXCH2 needs the tile face table", no);
+      if (m->d.OLx != m->d.OLy) return set_err("mgcm_init: pTracer%02d: cube multi-dimensional advection needs OLx = OLy", no);
+      if (m->d.OLx < 4 || m->d.OLy < 4)
+        return set_err("mgcm_init: pTracer%02d: multi-dimensional advection on the cube needs OLx, OLy >= 4 (GAD_CHECK: Overlap Size too small)", no);
+    }
+    if (!okScheme(s, "PTRACERS_vertAdvScheme"))
+      return set_err("mgcm_init: pTracer%02d: advScheme %d not implemented on the device", no, s);
+    const bool gm = m->p.useGMRedi && t.useGMRedi != 0;
+    if (gm && m->p.GM_AdvForm && m->p.multiDimAdvection && mdScheme(s))
+      return set_err("mgcm_init: pTracer%02d: GM_AdvForm with multi-dimensional advection is not implemented on the device", no);
+  }
   if (m->p.eosType != 0 && m->p.eosType != 1) return set_err("mgcm_init: eosType %d not implemented", m->p.eosType);
   if (m->d.Nr > 64) return set_err("mgcm_init: Nr = %d > 64 (column kernels hold a column in one workgroup)", m->d.Nr);
   if (m->p.periodicExternalForcing && (m->p.nForcRec < 1 || m->p.nForcRec > MG_MAXREC))
@@ -1536,6 +1665,8 @@ int mgcm_init(mgcm_model *m) {
     HIPCHK(calc_r_star(m));
     HIPCHK(hipStreamSynchronize(m->stream));
   }
+  m->ptrTabDirty = true;
+  if (ptr_tables_sync(m)) return -1;
   m->ready = true;
   return 0;
 }
@@ -1647,7 +1778,115 @@ static TracerArgs tracer_args(mgcm_model *m, bool salt) {
   return a;
 }
 
-// TEMP_INTEGRATE / SALT_INTEGRATE on stream `st` (the theta/salt ping-pong swap is host-side)
+// Passive tracer i (0-based) of PTRACERS_INTEGRATE (ptracers_integrate.F:150-420): salt's
+// sequence with the tracer's own parameters (PTRACERS_advScheme, _diffKh, _diffKr,
+// _useGMRedi), its own buffers and scratch, and the forcing restated from the reference's
+// experiment code (common.h TracerArgs).  flip: the parity the arguments are for.
+static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip) {
+  const Params &p = m->p;
+  const mgcm_model::PTracer &t = m->ptr[i];
+  TracerArgs a{};
+  a.tr = t.buf[flip];
+  a.trNext = t.buf[flip ^ 1];
+  a.gNm1 = t.gNm1;
+  a.scr = t.scr;
+  a.cp = t.adv1;   // (the marches' c': unused with multi-dimensional advection, as salt's advScr2)
+  a.sfc = nullptr;   // surfaceForcingPTr = 0 (PTRACERS_EvPrRn unset) unless the relaxation below
+  a.diffKh = t.diffKh;
+  a.diffKr = t.diffKr;
+  a.dT = p.deltaTtracer;
+  a.advection = 1;
+  a.forcing = 0;
+  const bool abScheme = t.advScheme == 2 || t.advScheme == 3 || t.advScheme == 4;
+  a.multiDim = p.multiDimAdvection && !abScheme;
+  a.useAB = abScheme;
+  a.limiter = t.advScheme == 33;
+  a.scheme = t.advScheme;
+  a.gNm2 = nullptr;   // (ADAMS_BASHFORTH3 is refused with passive tracers)
+  a.relaxRate = t.surfRelaxTau != 0.0 ? 1.0 / t.surfRelaxTau : 0.0;
+  a.relaxVal = t.surfRelaxVal;
+  a.src = t.interiorSource;
+  a.gm = p.useGMRedi && t.useGMRedi != 0;
+  a.adv1 = t.adv1; a.adv2 = t.adv2; a.gAdv = t.gAdv;
+  return a;
+}
+// MGCM_PTR_BATCH=1: the batched kernels wherever they apply (kernels_ptracers.hip ptr_batch_ok,
+// lat-lon maps); =0 and the default: one launch_tracer_step per tracer.  Read whenever
+// ptracers_on runs, which for forward_step is when a step graph is captured: the graph caches
+// are not keyed on the switch (nor on MGCM_STEP_FUSE), so a model that has captured its graphs
+// keeps their route whatever the variable says later (tools/ptracers_ab.py: one model per route).
+// The default is the measurement's (tools/ptracers_ab.py, profiles/r09/ptracers/): on
+// tutorial_global_oce_latlon the tracers run beside the 190 us pressure solve, where 4 tracers
+// cost nothing either way and the batched launches measured 1 % above the per-tracer ones in
+// every alternation (0.2575-0.2650 against 0.2547-0.2624 ms/step), although they take 57 us
+// of kernel time in 5 launches against 134 us in 20; at 8 tracers the per-tracer launches
+// outlast the solve (0.387 ms/step) and the batched ones do not (0.258): set it to 1 there.
+static bool ptr_batched(const mgcm_model *m) {
+  const char *e = getenv("MGCM_PTR_BATCH");
+  if (!e || atoi(e) == 0) return false;
+  return !m->uvMap && ptr_batch_ok(m->d, m->p);
+}
+// The batched kernels' device tables, one per parity: uploaded by mgcm_init and, after a
+// parameter change, by the next entry point that steps (never inside a graph capture)
+static int ptr_tables_sync(mgcm_model *m) {
+  const int n = (int)m->ptr.size();
+  if (!n || !m->ptrTabDirty) return 0;
+  std::vector<TracerArgs> tab(2 * (size_t)n);
+  for (int q = 0; q < 2; q++)
+    for (int i = 0; i < n; i++) tab[(size_t)q * n + i] = tracer_args_ptr(m, i, q);
+  // launch order: the GM/Redi tracers first (their own kernel), and in each kind the longest
+  // bodies first -- U3 / C4 inside GAD_CALC_RHS, then C2, then the multi-dimensional tracers
+  // (their advection ran in the passes)
+  std::vector<int> lists(2 * (size_t)n, 0);
+  m->ptrNMd = 0;
+  m->ptrNGM = 0;
+  int na = 0;
+  for (int cls = 0; cls < 6; cls++)
+    for (int i = 0; i < n; i++) {
+      const TracerArgs &a = tab[i];
+      const int c = (a.gm ? 0 : 3) + (a.multiDim ? 2 : (a.scheme == 2 ? 1 : 0));
+      if (c == cls) lists[n + na++] = i;
+    }
+  for (int i = 0; i < n; i++) {
+    if (tab[i].multiDim) lists[m->ptrNMd++] = i;
+    if (tab[i].gm) m->ptrNGM++;
+  }
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipMemcpy(m->d_ptrTab, tab.data(), tab.size() * sizeof(TracerArgs), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(m->d_ptrList, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice));
+  m->ptrTabDirty = false;
+  return 0;
+}
+// PTRACERS_INTEGRATE on stream `st`, after salt, and the tracers' part of
+// DO_FIELDS_BLOCKING_EXCHANGES right behind it on the same stream (nothing reads the new
+// tracers before the next step, so the end-of-step kernels stay as they are); then all pairs
+// swap together (CYCLE_TRACER)
+static int ptracers_on(mgcm_model *m, hipStream_t st, const Fields &F) {
+  const int n = (int)m->ptr.size();
+  if (!n) return 0;
+  if (m->ptrTabDirty) return set_err("ptracers_on: the passive tracers' device table is stale");
+  if (ptr_batched(m)) {
+    TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, F, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
+                                        m->ptrNGM, m->d_ctr, st));
+  } else {
+    for (int i = 0; i < n; i++) {
+      const TracerArgs a = tracer_args_ptr(m, i, m->ptrFlip);
+      Params pp = m->p;
+      pp.useGMRedi = a.gm;
+      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(F, a), a, m->d_ctr, st));
+    }
+  }
+  for (int i0 = 0; i0 < n; i0 += MG_XMAX) {
+    XFields x{};
+    for (int i = i0; i < n && i < i0 + MG_XMAX; i++) { x.p[x.n] = m->ptr[i].buf[m->ptrFlip ^ 1]; x.nz[x.n] = m->d.Nr; x.n++; }
+    TIMED(K_EXCH, launch_exchange_multi(m->d, x, m->d_halo, m->nHalo, nullptr, st));
+  }
+  m->ptrFlip ^= 1;
+  return 0;
+}
+
+// TEMP_INTEGRATE / SALT_INTEGRATE (and PTRACERS_INTEGRATE) on stream `st` (the ping-pong swaps are host-side)
 static int tracers_on(mgcm_model *m, hipStream_t st, const Fields *fo = nullptr) {
   const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
   const Fields &F = fo ? *fo : m->f;   // the fields the kernels read (fo: the hFac snapshot)
@@ -1655,7 +1894,7 @@ static int tracers_on(mgcm_model *m, hipStream_t st, const Fields *fo = nullptr)
     TIMED(K_TEMP, launch_tracer_hpair(m->d, m->p, F, aT, aS, m->d_ctr, st));
     std::swap(m->f.theta, m->f.thetaNext);
     std::swap(m->f.salt, m->f.saltNext);
-    return 0;
+    return ptracers_on(m, st, F);
   }
   if (m->p.tempStepping) {
     TIMED(K_TEMP, launch_tracer_step(m->d, m->p, F, tracer_args(m, false), m->d_ctr, st));
@@ -1665,11 +1904,11 @@ static int tracers_on(mgcm_model *m, hipStream_t st, const Fields *fo = nullptr)
     TIMED(K_TEMP, launch_tracer_step(m->d, m->p, F, tracer_args(m, true), m->d_ctr, st));
     std::swap(m->f.salt, m->f.saltNext);
   }
-  return 0;
+  return ptracers_on(m, st, F);
 }
 
 int mgcm_thermodynamics(mgcm_model *m) {
-  if (check_ready(m)) return -1;
+  if (check_ready(m) || ptr_tables_sync(m)) return -1;
   // forward_step.F:656 DO_OCEANIC_PHYS (every step: forcing records, EOS, GM tensor),
   // :732 THERMODYNAMICS (staggerTimeStep = F; the tracers only when stepped)
   TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream));
@@ -1758,7 +1997,7 @@ int mgcm_oceanic_phys(mgcm_model *m) {
 }
 
 int mgcm_tracer_step(mgcm_model *m) {
-  if (check_ready(m)) return -1;
+  if (check_ready(m) || ptr_tables_sync(m)) return -1;
   return tracers_on(m, m->stream);
 }
 
@@ -1811,9 +2050,10 @@ const char *mgcm_param_name(int i) {
 }
 
 long mgcm_field_count(mgcm_model *m, const char *name) {
-  const FieldDesc *fd = find_field(name);
-  if (!fd) { set_err("mgcm_field_count: unknown field %s", name); return -1; }
-  return field_count(m, fd->kind);
+  double *dev = nullptr;
+  long n = 0;
+  if (!lookup_field(m, name, &dev, &n)) { set_err("mgcm_field_count: unknown field %s", name); return -1; }
+  return n;
 }
 
 // tracers: 1 every field (the reference's set), 0 without theta/salt (exchanged beside the
@@ -1897,7 +2137,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   // staggerTimeStep (forward_step.F:1003-1036): THERMODYNAMICS after the pressure solve and
   // continuity, with the new velocities; DO_OCEANIC_PHYS still opens the step
   const bool stagger = m->p.staggerTimeStep != 0 && m->p.momStepping;
-  const bool tracers = m->p.tempStepping || m->p.saltStepping;
+  const bool tracers = m->p.tempStepping || m->p.saltStepping || !m->ptr.empty();
   const bool fork = !stagger && m->overlap && !m->timing && m->p.momStepping && tracers;
   bool endFused = false;   // CALC_R_STAR + blocking exchanges in one launch (below)
   bool stagEx = false;     // CALC_R_STAR + the staggered exchanges in one launch (below)
@@ -2008,6 +2248,9 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
                                      !pipe, !phiPipe));
       std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new tracers are the other buffers
       std::swap(m->f.salt, m->f.saltNext);
+      // PTRACERS_INTEGRATE where the fold replaced tracers_on: right behind it, before
+      // UPDATE_R_STAR rewrites the hFac it reads
+      if (ptracers_on(m, m->stream, m->f)) return -1;
     } else if (physPhi) TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, !ringAside && !ringPhys));
     else if (gmPhi) {
       TIMED(K_PHI, launch_gm_phi(m->d, m->p, m->f, m->stream));
@@ -2122,7 +2365,7 @@ static void drop_graphs(mgcm_model *m) {
 
 // Which theta/salt ping-pong buffers are current (the kernels' arguments differ).
 static int buffer_parity(const mgcm_model *m) {
-  return (m->f.theta == m->thetaA ? 0 : 1) + (m->f.salt == m->saltA ? 0 : 2);
+  return (m->f.theta == m->thetaA ? 0 : 1) + (m->f.salt == m->saltA ? 0 : 2) + (m->ptrFlip ? 4 : 0);
 }
 
 // Two FORWARD_STEPs captured once into a hipGraph per buffer parity (the tracer
@@ -2156,6 +2399,7 @@ static int one_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
   const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
   if (!m->graph1Exec[o][q][v]) {
     double *pre[4] = {m->f.theta, m->f.thetaNext, m->f.salt, m->f.saltNext};
+    const int preFlip = m->ptrFlip;
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
     const int rc = one_step(m, v ? STEP_LAST : STEP_PLAIN);
@@ -2170,13 +2414,17 @@ static int one_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
     double **tr[4] = {&m->f.theta, &m->f.thetaNext, &m->f.salt, &m->f.saltNext};
     for (int k = 0; k < 4; k++) m->graph1Tr[o][q][v][k] = *tr[k];
     m->f.theta = pre[0]; m->f.thetaNext = pre[1]; m->f.salt = pre[2]; m->f.saltNext = pre[3];
+    m->graph1Flip[o][q][v] = m->ptrFlip != 0;
+    m->ptrFlip = preFlip;
   }
   *out = m->graph1Exec[o][q][v];
   return 0;
 }
 int mgcm_tracer_parity(mgcm_model *m, int set) {
   if (set < 0) return buffer_parity(m);
-  if (set > 3) return set_err("mgcm_tracer_parity: parity %d outside 0..3", set);
+  const int top = m->ptr.empty() ? 3 : 7;   // bit 2: the passive tracers (all pairs swap together)
+  if (set > top) return set_err("mgcm_tracer_parity: parity %d outside 0..%d", set, top);
+  m->ptrFlip = (set & 4) ? 1 : 0;
   double *tB = m->f.theta == m->thetaA ? m->f.thetaNext : m->f.theta;
   double *sB = m->f.salt == m->saltA ? m->f.saltNext : m->f.salt;
   m->f.theta = (set & 1) ? tB : m->thetaA;
@@ -2190,6 +2438,7 @@ int mgcm_tracer_parity(mgcm_model *m, int set) {
 static void one_step_graph_done(mgcm_model *m, int o, int q, int v) {
   m->f.theta = m->graph1Tr[o][q][v][0]; m->f.thetaNext = m->graph1Tr[o][q][v][1];
   m->f.salt = m->graph1Tr[o][q][v][2]; m->f.saltNext = m->graph1Tr[o][q][v][3];
+  m->ptrFlip = m->graph1Flip[o][q][v] ? 1 : 0;
 }
 
 static int ovl_trial(mgcm_model *m);
@@ -2198,7 +2447,7 @@ static int ovl_trial(mgcm_model *m);
 // undecided, runs its trial now (on a copy of the state) so that no later timed batch
 // contains the trial's 20 steps.
 int mgcm_prepare(mgcm_model *m) {
-  if (check_ready(m)) return -1;
+  if (check_ready(m) || ptr_tables_sync(m)) return -1;
   if (!m->useGraph) return 0;
   HIPCHK(hipSetDevice(m->device));
   if (m->ovlAuto && !m->ovlDecided && ovl_trial(m)) return -1;
@@ -2213,13 +2462,17 @@ int mgcm_prepare(mgcm_model *m) {
 // graphs each, bracketed by events -- and the state is copied back, so the caller's steps
 // are untouched; the faster graph is kept.  Both graphs compute identical results.
 static int ovl_trial(mgcm_model *m) {
-  const bool forkable = !m->p.staggerTimeStep && m->p.momStepping && (m->p.tempStepping || m->p.saltStepping);
+  // (one_step's `tracers`: theta, salt or passive tracers)
+  const bool forkable = !m->p.staggerTimeStep && m->p.momStepping &&
+                        (m->p.tempStepping || m->p.saltStepping || !m->ptr.empty());
   if (!forkable) { m->ovlDecided = true; return 0; }   // one_step never forks: nothing to choose
   std::vector<std::pair<void *, size_t>> parts = {
       {m->f.a2, (size_t)F2_COUNT * m->d.N2all * sizeof(double)},
       {m->f.a3, (size_t)F3_COUNT * m->d.N3all * sizeof(double)},
       {m->d_ctr, 2 * sizeof(int)},
       {m->d_rec, (size_t)m->maxRec * sizeof(SolveRecord)}};
+  // (the passive tracers' arena too: the trial's steps must not leak into the caller's tracers)
+  if (!m->ptr.empty()) parts.push_back({m->a4, m->ptr.size() * PTR_NF * (size_t)m->d.N3all * sizeof(double)});
   for (auto &fd : FIELDS)
     if (fd.kind != F2D && fd.kind != F3D && field_ptr(m, &fd))
       parts.push_back({field_ptr(m, &fd), (size_t)field_count(m, fd.kind) * sizeof(double)});
@@ -2271,7 +2524,7 @@ static int ovl_trial(mgcm_model *m) {
 }
 
 int mgcm_forward_step(mgcm_model *m, int nsteps) {
-  if (check_ready(m)) return -1;
+  if (check_ready(m) || ptr_tables_sync(m)) return -1;
   if (land_guard_check(m, "mgcm_forward_step")) return -1;
   if (nsteps <= 0 || nsteps > m->maxRec) return set_err("mgcm_forward_step: nsteps %d out of range", nsteps);
   HIPCHK(hipSetDevice(m->device));
@@ -2315,6 +2568,9 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
 int mgcm_set_tile_range(mgcm_model *m, int t0, int nT) {
   if (t0 < 0 || nT < 1 || t0 + nT > m->d.nTiles)
     return set_err("mgcm_set_tile_range: tiles [%d, %d) outside [0, %d)", t0, t0 + nT, m->d.nTiles);
+  if (!m->ptr.empty() && nT < m->d.nTiles)
+    return set_err("mgcm_set_tile_range: passive tracers are not supported in tile-sharded runs (tile range [%d, %d) of %d)",
+                   t0, t0 + nT, m->d.nTiles);
   if (m->solver == Cg2dSolver::MwgRef && nT < m->d.nTiles)
     return set_err("mgcm_set_tile_range: cg2dRefOrder in the multi-workgroup CG2D needs the whole domain's tiles, not the "
                    "tile range [%d, %d) of %d", t0, t0 + nT, m->d.nTiles);
@@ -2513,6 +2769,7 @@ static int shard_join_thermo(mgcm_model *m) {
 int mgcm_step_phase(mgcm_model *m, int phase) {
   if (check_ready(m)) return -1;
   if (!m->p.momStepping) return set_err("mgcm_step_phase: requires momStepping");
+  if (!m->ptr.empty()) return set_err("mgcm_step_phase: passive tracers are not supported by the tile-sharded driver");
   const bool stagger = m->p.staggerTimeStep != 0;
   const bool tracers = m->p.tempStepping || m->p.saltStepping;
   switch (phase) {

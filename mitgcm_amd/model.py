@@ -47,10 +47,48 @@ def _dp(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+PTRACER_PARAMS = ("advScheme", "diffKh", "diffKr", "useGMRedi", "surfRelaxTau", "surfRelaxVal", "interiorSource",
+                  "EvPrRn")
+PTRACERS_MAX = 99   # PTRACERS_SIZE.h: two digits in every name
+
+
+def ptracer_name(i):
+    """Field name of passive tracer i (1-based): 'pTracer01' .. 'pTracer99'."""
+    if not 1 <= int(i) <= PTRACERS_MAX:
+        raise ValueError("passive tracer %r outside 1..%d" % (i, PTRACERS_MAX))
+    return "pTracer%02d" % int(i)
+
+
+def ptracer_index(name):
+    """The 1-based tracer number of 'pTracerNN' / 'gpTrNm1_NN', None for any other name."""
+    for pre in ("pTracer", "gpTrNm1_"):
+        if name.startswith(pre) and len(name) == len(pre) + 2 and name[len(pre):].isdigit():
+            i = int(name[len(pre):])
+            return i if 1 <= i <= PTRACERS_MAX else None
+    return None
+
+
+def check_ptracer_specs(specs):
+    """Argument errors of a passive-tracer list, before anything reaches the device."""
+    specs = list(specs)
+    if not 1 <= len(specs) <= PTRACERS_MAX:
+        raise ValueError("%d passive tracers outside 1..%d" % (len(specs), PTRACERS_MAX))
+    for no, sp in enumerate(specs, 1):
+        if not isinstance(sp, dict):
+            raise TypeError("passive tracer %d: a dict of parameters expected, got %r" % (no, type(sp).__name__))
+        bad = sorted(set(sp) - set(PTRACER_PARAMS) - {"init", "name"})
+        if bad:
+            raise ValueError("passive tracer %d: unknown parameter(s) %s" % (no, ", ".join(bad)))
+    return specs
+
+
 class Model:
-    def __init__(self, grid, params, device=0):
+    def __init__(self, grid, params, device=0, ptracers=None):
         self.g = grid
         self.params = dict(params)
+        self.ptracers = []
+        if ptracers is not None:
+            ptracers = check_ptracer_specs(ptracers)
         L = lib()
         g = grid
         self.h = L.mgcm_create(g.sNx, g.sNy, g.OLx, g.OLy, g.Nr, g.nSx, g.nSy, device)
@@ -86,6 +124,35 @@ class Model:
                                          for t in range(1, topo.nTiles + 1)], dtype=np.int32)
             check(L.mgcm_set_uv_map(self.h, LP(u1), LP(v1), LP(u0), LP(v0), IP(face), IP(edge), u1.size),
                   "mgcm_set_uv_map")
+        if ptracers is not None:
+            self.add_ptracers(ptracers)
+
+    def add_ptracers(self, specs):
+        """pkg/ptracers: allocate len(specs) passive tracers (before init()) and set each one's
+        parameters (PTRACER_PARAMS) and initial field ('init': a scalar or a (nTiles, Nr, ny, nx)
+        array, halos included; default 0, the reference's with no PTRACERS_initialFile)."""
+        specs = check_ptracer_specs(specs)
+        L = lib()
+        check(L.mgcm_ptracers_alloc(self.h, len(specs)), "mgcm_ptracers_alloc")
+        self.ptracers = [dict(sp) for sp in specs]
+        g = self.g
+        # A model-wide side effect (README, "Passive tracers"): multiDimAdvection is .TRUE. by
+        # default in the reference (set_defaults.F); a configuration whose theta and salt never
+        # needed it leaves it unset, which the device takes as off, and a DST tracer needs it.
+        # An explicit 0 is left alone: mgcm_init then refuses the tracer's scheme.
+        if "multiDimAdvection" not in self.params and any(int(sp.get("advScheme", 2)) in (30, 33) for sp in specs):
+            self.params["multiDimAdvection"] = 1
+            check(L.mgcm_set_param(self.h, b"multiDimAdvection", 1.0), "mgcm_set_param(multiDimAdvection)")
+        for no, sp in enumerate(specs, 1):
+            for k in PTRACER_PARAMS:
+                if k in sp:
+                    check(L.mgcm_ptracer_param(self.h, no, k.encode(), float(sp[k])), "mgcm_ptracer_param(%s)" % k)
+            if sp.get("init") is not None:
+                a = np.asarray(sp["init"], dtype=np.float64)
+                self.put(ptracer_name(no), np.broadcast_to(a, (g.nTiles, g.Nr, g.ny, g.nx)) if a.ndim == 0 else a)
+
+    def ptracer_param(self, i, name):
+        return lib().mgcm_ptracer_param_get(self.h, int(i), name.encode())
 
     def init(self):
         check(lib().mgcm_init(self.h), "mgcm_init")
@@ -106,7 +173,7 @@ class Model:
         g = self.g
         if name in GRID_1D or name in STATE_1D:
             return (g.Nr + 1,)
-        if name in GRID_3D or name in STATE_3D or name in WORK_3D:
+        if name in GRID_3D or name in STATE_3D or name in WORK_3D or ptracer_index(name) is not None:
             return (g.nTiles, g.Nr, g.ny, g.nx)
         if name == "forcRec":   # 6 forcing fields x the device's record capacity, 2-D each
             n = lib().mgcm_field_count(self.h, b"forcRec")
@@ -160,6 +227,10 @@ class Model:
 
     def sync(self):
         check(lib().mgcm_sync(self.h), "mgcm_sync")
+
+    def trcstat(self):
+        """MONITOR's trcstat block of the passive tracers (module function trcstat)."""
+        return trcstat(self)
 
     def solve_stats(self, back=0):
         f, la, rm = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
@@ -312,6 +383,26 @@ def mon_stats(g, arr, hfac, mask, area, dr):
             sds.append(sd)
         theSD = np.sqrt(gs(sds) / theVol)
     return {"min": theMin, "max": theMax, "mean": theMean, "sd": theSD, "del2": theDel2}
+
+
+def trcstat_fields(g, tracers, hFacC=None):
+    """MON_CALC_STATS_RL of each passive tracer field (host arrays, (nTiles, Nr, ny, nx)) with
+    hFacC (default: the grid's), maskInC, rA, drF: trcstat_ptracerNN_{max,min,mean,sd,del2}."""
+    f = g.f
+    hC = f["hFacC"] if hFacC is None else hFacC
+    out = {}
+    for no, arr in enumerate(tracers, 1):
+        st = mon_stats(g, np.asarray(arr, dtype=np.float64), hC, f["maskInC"], f["rA"], f["drF"])
+        for k, v in st.items():
+            out["trcstat_ptracer%02d_%s" % (no, k)] = float(v)
+    return out
+
+
+def trcstat(model):
+    """The trcstat block of MONITOR for a model's passive tracers (pkg/ptracers/ptracers_monitor.F),
+    from the downloaded tracers and the current hFacC (r*: updated every step on the device)."""
+    return trcstat_fields(model.g, [model.get(ptracer_name(no)) for no in range(1, len(model.ptracers) + 1)],
+                          model.get("hFacC"))
 
 
 def dynstat(model):

@@ -123,4 +123,100 @@ def write_pickup(model, directory, simulation="mitgcm_amd"):
     if p.get("useCDscheme", 0):
         cd = {n: model.get(n) for n in ("uVelD", "vVelD", "uNM1", "vNM1", "etaNm1")}
     write_pickup_fields(model.g, p, fields, directory, myIter, myTime, simulation, cd)
+    if getattr(model, "ptracers", None):
+        n = len(model.ptracers)
+        write_pickup_ptracers_fields(model.g, [model.get("pTracer%02d" % i) for i in range(1, n + 1)],
+                                     {i: model.get("gpTrNm1_%02d" % i) for i in range(1, n + 1)
+                                      if ptracer_is_ab(model.ptracers[i - 1])},
+                                     directory, myIter, myTime, simulation)
     return myIter
+
+
+# ---- pkg/ptracers: pickup_ptracers.<iter> (pkg/ptracers/ptracers_write_pickup.F:93-141) ----------
+# MDS records of Nr levels each (WRITE_REC_3D_RL, precFloat64): pTracer of every tracer in use,
+# 'pTrNN', then gpTrNm1 of every tracer stepped with Adams-Bashforth on its tendency
+# (PTRACERS_AdamsBashGtr: schemes 2, 3, 4), 'gPtrNNm1'; NN = PTRACERS_ioLabel, two digits.
+def ptracer_is_ab(spec):
+    """PTRACERS_AdamsBashGtr of a tracer spec: AB2 on the tendency (gad_init_fixed.F's C2, U3, C4)."""
+    return int(spec.get("advScheme", 2)) in (2, 3, 4)
+
+
+def write_meta_3d(path, simulation, Nx, Ny, Nr, nrec, myIter, myTime, flds):
+    """MDS_WR_METAFILES for a global file of 3-D records."""
+    lines = [" simulation = { '%s' };" % simulation,
+             " nDims = [%4d ];" % 3,
+             " dimList = [",
+             "%6d,%5d,%5d," % (Nx, 1, Nx),
+             "%6d,%5d,%5d," % (Ny, 1, Ny),
+             "%6d,%5d,%5d" % (Nr, 1, Nr),
+             " ];",
+             " dataprec = [ 'float64' ];",
+             " nrecords = [%6d ];" % nrec,
+             " timeStepNumber = [%11d ];" % myIter,
+             " timeInterval = [%20.12E ];" % myTime,
+             " nFlds = [%5d ];" % len(flds), " fldList = {",
+             " " + " ".join("'%-8s'" % f for f in flds), " };"]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def write_pickup_ptracers_fields(g, tracers, gnm1, directory, myIter, myTime, simulation="mitgcm_amd"):
+    """pickup_ptracers.<iter>.data/.meta from tile-layout host arrays: tracers[i] (nTiles, Nr, ny, nx)
+    of tracer i+1, gnm1 {tracer number: gpTrNm1} of the Adams-Bashforth tracers."""
+    blocks, flds = [], []
+    for no, a in enumerate(tracers, 1):
+        blocks.append(tiles_to_global(g, np.moveaxis(np.asarray(a, dtype=np.float64), 0, 1)))
+        flds.append("pTr%02d" % no)
+    for no in sorted(gnm1):
+        blocks.append(tiles_to_global(g, np.moveaxis(np.asarray(gnm1[no], dtype=np.float64), 0, 1)))
+        flds.append("gPtr%02dm1" % no)
+    data = np.stack(blocks)                       # (records, Nr, Ny, Nx)
+    Nr, Ny, Nx = data.shape[1:]
+    base = os.path.join(directory, "pickup_ptracers.%010d" % myIter)
+    data.astype(">f8").tofile(base + ".data")
+    write_meta_3d(base + ".meta", simulation, Nx, Ny, Nr, data.shape[0], myIter, myTime, flds)
+    return base
+
+
+def read_pickup_ptracers(g, base):
+    """Read pickup_ptracers (base: the path without .data/.meta) back into tile layout with the
+    halos exchanged: (tracers, gnm1) as write_pickup_ptracers_fields takes them, by the .meta's
+    field list (PTRACERS_READ_PICKUP reads by name too, ptracers_read_pickup.F)."""
+    import re
+    from .configs import _to_tiles
+    meta = open(base + ".meta").read()
+    flds = re.findall(r"'([^']*)'", meta[meta.index("fldList"):])
+    dims = [int(x) for x in re.findall(r"^\s*(\d+),\s*1,", meta, re.M)]
+    Nx, Ny, Nr = dims[:3]
+    nrec = int(re.search(r"nrecords = \[\s*(\d+)", meta).group(1))
+    if len(flds) != nrec:
+        raise ValueError("%s.meta: %d fields for %d records" % (base, len(flds), nrec))
+    data = np.fromfile(base + ".data", dtype=">f8").astype(np.float64)
+    if data.size != nrec * Nr * Ny * Nx:
+        raise ValueError("%s.data: %d values, the .meta says %d" % (base, data.size, nrec * Nr * Ny * Nx))
+    data = data.reshape(nrec, Nr, Ny, Nx)
+    tracers, gnm1 = {}, {}
+    for rec, name in zip(data, (f.strip() for f in flds)):
+        arr = np.moveaxis(_to_tiles(g, rec), 0, 1).copy()     # (nTiles, Nr, ny, nx)
+        mt, mg = re.fullmatch(r"pTr(\d\d)", name), re.fullmatch(r"gPtr(\d\d)m1", name)
+        if mt:
+            tracers[int(mt.group(1))] = arr
+        elif mg:
+            gnm1[int(mg.group(1))] = arr
+        else:
+            raise ValueError("%s.meta: unknown field %r" % (base, name))
+    if sorted(tracers) != list(range(1, len(tracers) + 1)):
+        raise ValueError("%s.meta: tracers %s are not 1..n" % (base, sorted(tracers)))
+    return [tracers[i] for i in sorted(tracers)], gnm1
+
+
+def load_pickup_ptracers(model, directory, myIter):
+    """PTRACERS_READ_PICKUP for a device model: its passive tracers and AB2 histories from
+    pickup_ptracers.<myIter> (the halos of gpTrNm1 are not read by any kernel)."""
+    tracers, gnm1 = read_pickup_ptracers(model.g, os.path.join(directory, "pickup_ptracers.%010d" % myIter))
+    if len(tracers) != len(model.ptracers):
+        raise ValueError("pickup_ptracers holds %d tracers, the model %d" % (len(tracers), len(model.ptracers)))
+    for no, a in enumerate(tracers, 1):
+        model.put("pTracer%02d" % no, a)
+    for no, a in gnm1.items():
+        model.put("gpTrNm1_%02d" % no, a)
