@@ -10,13 +10,12 @@ namespace mgcm {
 int cg2d_bxy_variants();
 // geometry of variant v; -1 when v names none
 int cg2d_bxy_geometry(int v, int *bx, int *by, int *nt);
-// nbx / blkx / nBlk: the block tables of variant v (model.hip build_bxy).  slot2 (or nullptr):
-// the 2-D point -> LDS slot map of the fused EXCH(cg2d_x) + etaN epilogue, read through srcOf.
+// nbx / blkx / nBlk: the block tables of variant v (model.hip build_bxy).
 // dropG / nDrop / guardHit: the points of the all-land blocks the tables leave out, scanned for
 // a non-zero by the prologue, and the word it sets on one (nullptr, 0, nullptr: none left out).
 hipError_t launch_cg2d_bxy(int v, const Dims &d, const Params &p, const Fields &f, const unsigned *nbx, const int *blkx,
-                           int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *slot2,
-                           const long *srcOf, const int *dropG, int nDrop, int *guardHit, hipStream_t s);
+                           int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *dropG,
+                           int nDrop, int *guardHit, hipStream_t s);
 
 // ---- k_cg2d_block: one point-per-thread workgroup of 1024 summing in the reference's order
 // (cg2dRefOrder), up to cg2d_ref_max_points() points (kernels_solve.hip)

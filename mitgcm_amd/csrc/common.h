@@ -262,22 +262,15 @@ inline size_t mg_colf_lds(int Nr, int nc, int nArr) { return (size_t)nArr * Nr *
 inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + nc - 1) / nc); }
 // Launch fusions of FORWARD_STEP, each switchable for A/B runs: MGCM_STEP_FUSE = bit mask of
 // the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
-// MG_FUSE_ETA EXCH(cg2d_x) + etaN in the single-workgroup CG2D, MG_FUSE_PHI CALC_PHI_HYD +
-// del2uv in one grid, MG_FUSE_END CALC_R_STAR + the blocking exchanges in one grid,
-// MG_FUSE_PHYS DO_OCEANIC_PHYS + CALC_PHI_HYD in one column pass (bit-identical, but on LLC-90
-// 226-313 us against 75 + 77 for the two launches: the per-point EOS loads lose their
-// plane-wide parallelism inside the column frame; profiles/r03/phys/), MG_FUSE_ETAA
-// SOLVE_FOR_PRESSURE's EXCH(cg2d_x) + etaN off the critical path (exactConserv: beside the
-// correction step, which derives the eta it needs from cg2d_x itself; bit-identical, but the
-// third stream's fork and join cost more than the launch they hide: config 2 0.343 against
-// 0.330 ms/step, config 3 0.454 against 0.429; profiles/r03/fuseab/), MG_FUSE_TREX the
+// MG_FUSE_PHI CALC_PHI_HYD + del2uv in one grid, MG_FUSE_END CALC_R_STAR + the blocking
+// exchanges in one grid, MG_FUSE_TREX the
 // tracers' halo exchange on their own stream beside the pressure solve (late join only;
 // bit-identical, no measurable change on LLC-90: 1.851 against 1.851-1.854 ms/step).
 // MG_FUSE_DT THERMODYNAMICS' tracer kernels folded into DYNAMICS' launches instead of a
 // second stream beside them (kernels_step.hip; early fork only, small grids), MG_FUSE_ETAX
-// no separate EXCH(cg2d_x) + etaN under exactConserv (one_step), MG_FUSE_OPE UPDATE_CG2D's
+// no separate EXCH(cg2d_x) + etaN under exactConserv (plan_step), MG_FUSE_OPE UPDATE_CG2D's
 // operator and preconditioner in the fold's first two grids (ucg2d.h; r*, with MG_FUSE_DT),
-// MG_FUSE_RING the VI path's halo-ring AB2 on the tracers' stream (late fork, one_step),
+// MG_FUSE_RING the VI path's halo-ring AB2 on the tracers' stream (late fork, plan_step),
 // MG_FUSE_RINGP that ring in DO_OCEANIC_PHYS's grid instead where there is no late fork
 // (k_phys_ring: the staggered cube), MG_FUSE_ENDS CALC_R_STAR and
 // DO_STAGGER_FIELDS_EXCHANGES' u, v, w in one grid (k_rstar_exmix: the staggered cube),
@@ -286,16 +279,45 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 // MG_PIPE_MIN_STEPS steps or more; one_step's StepMode, model.hip), MG_FUSE_PHIP (with
 // MG_FUSE_PIPE) the next step's CALC_PHI_HYD and del2uv in this step's CALC_R_STAR + exchange grid
 // (k_rstar_exch_phi, kernels_step.hip): the pipelined step then starts at the momentum launch.
-enum { MG_FUSE_SFP = 1, MG_FUSE_ETA = 2, MG_FUSE_PHI = 4, MG_FUSE_END = 8, MG_FUSE_PHYS = 16, MG_FUSE_ETAA = 32,
-       MG_FUSE_TREX = 64, MG_FUSE_DT = 128, MG_FUSE_ETAX = 256, MG_FUSE_TCG = 512, MG_FUSE_OPE = 1024,
-       MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384, MG_FUSE_PHIP = 32768 };
-inline bool mg_fuse_on(int bit) {
+// The step's fusions are decided in one place, model.hip's plan_step; the kernel files' own
+// *_fusable / *_ok predicates, which it calls, read their bits here too.
+// Four bits are retired (round 10): each was off by default, bit-identical and measured slower
+// wherever it was tried, and mgcm_init refuses a mask that sets one (mg_fuse_retired) -- an A/B
+// script must never measure something other than what it asked for:
+//   2   EXCH(cg2d_x) + etaN in the single-workgroup CG2D's epilogue: +4 us/step on config 2 (one
+//       CU walking every 2-D point costs more than the launch it saves);
+//   16  DO_OCEANIC_PHYS + CALC_PHI_HYD in one column pass: on LLC-90 226-313 us against 75 + 77
+//       for the two launches -- the per-point EOS loads lose their plane-wide parallelism inside
+//       the column frame (profiles/r03/phys/);
+//   32  SOLVE_FOR_PRESSURE's EXCH(cg2d_x) + etaN on a third stream beside the correction step
+//       (exactConserv): the fork and join cost more than the launch they hide -- config 2 0.343
+//       against 0.330 ms/step, config 3 0.454 against 0.429 (profiles/r03/fuseab/); superseded
+//       by MG_FUSE_ETAX, which launches nothing;
+//   512 THERMODYNAMICS beside the pressure solve under r*, reading a copy of hFac taken before
+//       UPDATE_R_STAR rewrites it: on config 2 the fold into DYNAMICS' launches stays faster,
+//       0.2885 against 0.307 ms/step (profiles/r04/tcg/) -- the tracers' launches beside
+//       DYNAMICS cost more than the 190 us single-CU solve they could hide behind.
+// The twelve others keep their values (tests and tools pass numeric masks).
+enum { MG_FUSE_SFP = 1, MG_FUSE_PHI = 4, MG_FUSE_END = 8, MG_FUSE_TREX = 64, MG_FUSE_DT = 128, MG_FUSE_ETAX = 256,
+       MG_FUSE_OPE = 1024, MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384,
+       MG_FUSE_PHIP = 32768 };
+inline int mg_fuse_mask() {
   // read per call (tests switch it per model)
-  const int mask = getenv("MGCM_STEP_FUSE") ? atoi(getenv("MGCM_STEP_FUSE"))
-                                            : MG_FUSE_SFP | MG_FUSE_PHI | MG_FUSE_END | MG_FUSE_DT | MG_FUSE_ETAX |
-                                                MG_FUSE_OPE | MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE |
-                                                MG_FUSE_PHIP;
-  return (mask & bit) != 0;
+  return getenv("MGCM_STEP_FUSE") ? atoi(getenv("MGCM_STEP_FUSE"))
+                                  : MG_FUSE_SFP | MG_FUSE_PHI | MG_FUSE_END | MG_FUSE_DT | MG_FUSE_ETAX | MG_FUSE_OPE |
+                                        MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE | MG_FUSE_PHIP;
+}
+inline bool mg_fuse_on(int bit) { return (mg_fuse_mask() & bit) != 0; }
+// the lowest retired bit the mask sets (0: none), and what it selected
+inline int mg_fuse_retired(const char **what) {
+  static const struct { int bit; const char *what; } R[] = {
+      {2, "EXCH(cg2d_x) + etaN in the single-workgroup CG2D's epilogue"},
+      {16, "DO_OCEANIC_PHYS + CALC_PHI_HYD in one column pass"},
+      {32, "EXCH(cg2d_x) + etaN on a third stream"},
+      {512, "THERMODYNAMICS beside the pressure solve under r*"}};
+  for (const auto &r : R)
+    if (mg_fuse_mask() & r.bit) { *what = r.what; return r.bit; }
+  return 0;
 }
 // Horizontal launch fusion of two independent latency-bound kernels into one grid: on the
 // small configurations only (up to 2^21 grid points), where each launch is a few us of latency

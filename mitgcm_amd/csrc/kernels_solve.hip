@@ -1405,8 +1405,16 @@ int cg2d_bxy_geometry(int v, int *bx, int *by, int *nt) {
 }
 template <int BX, int BY, int NT>
 static hipError_t launch_bxy_t(const Dims &d, const Params &p, const Fields &f, const unsigned *nbx, const int *blkx,
-                               int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *slot2,
-                               const long *srcOf, const int *dropG, int nDrop, int *guardHit, hipStream_t s) {
+                               int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *dropG,
+                               int nDrop, int *guardHit, hipStream_t s) {
+  // The kernel's slot2 / srcOf parameters and the epilogue behind `if (slot2)` (EXCH(cg2d_x) + etaN
+  // in the solver, MGCM_STEP_FUSE bit 2, retired in round 10: nothing builds its table any more)
+  // are never entered.  They stay in the kernel because its code without them measured slower:
+  // <3, 2, 512, false, true, false> 168.7-169.8 against 168.0-168.3 us per solve and config 2
+  // 0.2536-0.2539 against 0.2511-0.2532 ms/step in five alternations, where this form, the
+  // parent's code byte for byte, ran 0.2519-0.2529 (profiles/r10/step_plan/); not tuned here
+  const int *slot2 = nullptr;
+  const long *srcOf = nullptr;
   if (nBlk > NT) return hipErrorInvalidValue;
   const bool mr = nIterMin >= 0, fm = p.cg2dUseFMA != 0, sr = p.useSRCGSolver != 0;
   const size_t lds = (2 * ((size_t)BX * BY * NT + 1) + 4 * 16 + 2) * sizeof(double);
@@ -1426,13 +1434,12 @@ static hipError_t launch_bxy_t(const Dims &d, const Params &p, const Fields &f, 
                      srcOf, dropG, nDrop, guardHit);
   return hipGetLastError();
 }
-// slot2 (or nullptr): the 2-D point -> LDS slot map of the fused EXCH(cg2d_x) + etaN epilogue
 hipError_t launch_cg2d_bxy(int v, const Dims &d, const Params &p, const Fields &f, const unsigned *nbx, const int *blkx,
-                           int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *slot2,
-                           const long *srcOf, const int *dropG, int nDrop, int *guardHit, hipStream_t s) {
+                           int nBlk, int maxIters, int nIterMin, SolveRecord *rec, int *stepCounter, const int *dropG,
+                           int nDrop, int *guardHit, hipStream_t s) {
 #define CGX_CASE(V, BX, BY, NT)                                                                                  \
   case V:                                                                                                        \
-    return launch_bxy_t<BX, BY, NT>(d, p, f, nbx, blkx, nBlk, maxIters, nIterMin, rec, stepCounter, slot2, srcOf, dropG, \
+    return launch_bxy_t<BX, BY, NT>(d, p, f, nbx, blkx, nBlk, maxIters, nIterMin, rec, stepCounter, dropG, \
                                     nDrop, guardHit, s);
   switch (v) {
     CGX_CASE(0, 2, 4, 512)

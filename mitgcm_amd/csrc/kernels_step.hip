@@ -315,7 +315,7 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
 // needs only what step n's last launch (k_rstar_exch) produces: the halos of u and v, each a copy
 // of the value at its exchange source, and the r* factors, each a few flops on the eta the
 // correction step left.  So it runs as further logical blocks of that grid, reading u and v at
-// the sources and forming the factors itself (kernels_dyn.hip phi_hyd_body<.., HO>,
+// the sources and forming the factors itself (kernels_dyn.hip phi_hyd_body<HO>,
 // del2uv_body<HO>; rstar.h), and step n+1 starts at k_dt_l2.  No block reads a location another
 // block of the grid writes.  Longest body first:
 //   [CALC_PHI_HYD(n+1) column frame | CALC_R_STAR + UPDATE_ETAH | blocking exchanges | del2uv(n+1)]
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(256) k_rstar_exch_phi(Dims d, Params p, Fields
                                                         int nbX, int nzMax, int nbXall, int fromX, int empNext, int nc,
                                                         int nbPhi) {
   int lb = mg_xcd_block();
-  if (lb < nbPhi) { phi_hyd_body<false, true>(d, p, f, nc, lb, nullptr, srcOf, fromX); return; }
+  if (lb < nbPhi) { phi_hyd_body<true>(d, p, f, nc, lb, srcOf, fromX); return; }
   lb -= nbPhi;
   if (lb < nbR) { calc_r_star_body<true>(d, p, f, srcOf, lb, fromX, empNext); return; }
   lb -= nbR;

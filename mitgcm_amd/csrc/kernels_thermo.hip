@@ -1248,55 +1248,33 @@ hipError_t launch_gm_tensor(const Dims &d, const Params &p, const Fields &f, hip
   return hipGetLastError();
 }
 
-// The hFac THERMODYNAMICS reads, copied before UPDATE_R_STAR(.TRUE.) rewrites them (one_step's
-// MG_FUSE_TCG layout): hFacC, hFacW, hFacS and their reciprocals into snap[6 x N3all]; the
-// tracer kernels then get the Fields with those six pointers moved to the copy.
-struct Snap6 {
-  const double *src[6];
-  double *dst[6];
-};
-__global__ void __launch_bounds__(256) k_hfac_snapshot(Snap6 sn, long n) {
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= n) return;
-  const int a = (int)blockIdx.y;
-  sn.dst[a][q] = sn.src[a][q];
-}
-Fields hfac_snapshot_fields(const Dims &d, const Fields &f, double *snap) {
-  Fields g = f;
-  g.hFacC = snap; g.hFacW = snap + d.N3all; g.hFacS = snap + 2 * d.N3all;
-  g.recip_hFacC = snap + 3 * d.N3all; g.recip_hFacW = snap + 4 * d.N3all; g.recip_hFacS = snap + 5 * d.N3all;
-  return g;
-}
-hipError_t launch_hfac_snapshot(const Dims &d, const Fields &f, double *snap, hipStream_t s) {
-  const Fields g = hfac_snapshot_fields(d, f, snap);
-  Snap6 sn{{f.hFacC, f.hFacW, f.hFacS, f.recip_hFacC, f.recip_hFacW, f.recip_hFacS},
-           {g.hFacC, g.hFacW, g.hFacS, g.recip_hFacC, g.recip_hFacW, g.recip_hFacS}};
-  const long n = d.N3all;
-  hipLaunchKernelGGL(k_hfac_snapshot, dim3((unsigned)((n + 255) / 256), 6), dim3(256), 0, s, sn, n);
-  return hipGetLastError();
-}
-
 hipError_t launch_phys_ring(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s);
-// ringDone non-null: the per-point form takes the VI path's halo-ring AB2 into its grid
-// (k_phys_ring) and sets *ringDone; the 16-byte form does not
-hipError_t launch_oceanic_phys(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s, bool gm,
-                               bool *ringDone) {
+// the 16-byte form (k_oceanic_phys2) or the per-point one
+static bool phys_v2(const Dims &d, const Params &p, const Fields &f) {
   auto al = [](const void *q) { return ((uintptr_t)q & 15u) == 0; };
   const int v2Env = getenv("MGCM_PHYS_V2") ? atoi(getenv("MGCM_PHYS_V2")) : 1;
   // (large grids only: on config 2's 70 k points per level set, half the threads cost more
   // than the wider accesses save -- 12.9 against 10.1 us, the surface level's forcing
   // interpolation then serial in each thread)
   const bool big = (long)d.n2 * d.nT * d.Nr >= (1L << 21);
-  const bool v2 = v2Env != 0 && (big || v2Env == 2) && (d.n2 & 1) == 0 && (d.n3 & 1) == 0 && al(f.theta) && al(f.salt) && al(f.maskC) &&
-                  al(f.rhoInSitu) && al(f.IVDConvCount) && (!p.useGMRedi || al(f.sigmaR)) &&
-                  (p.eosType != 1 || p.selectP_inEOS_Zc != 2 || al(f.totPhiHyd));
+  return v2Env != 0 && (big || v2Env == 2) && (d.n2 & 1) == 0 && (d.n3 & 1) == 0 && al(f.theta) && al(f.salt) && al(f.maskC) &&
+         al(f.rhoInSitu) && al(f.IVDConvCount) && (!p.useGMRedi || al(f.sigmaR)) &&
+         (p.eosType != 1 || p.selectP_inEOS_Zc != 2 || al(f.totPhiHyd));
+}
+// whether DO_OCEANIC_PHYS's launch can take the VI path's halo-ring AB2 into its grid
+// (k_phys_ring): the per-point form does, the 16-byte form does not
+bool phys_ring_ok(const Dims &d, const Params &p, const Fields &f) { return !phys_v2(d, p, f); }
+// ring (phys_ring_ok must hold): the halo-ring AB2 in the same grid
+hipError_t launch_oceanic_phys(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s, bool gm,
+                               bool ring) {
+  const bool v2 = phys_v2(d, p, f);
+  if (ring && v2) return hipErrorInvalidValue;
   if (v2) {
     const unsigned nb = (unsigned)(((d.n2 >> 1) + 255) / 256);
     hipLaunchKernelGGL(k_oceanic_phys2, dim3(nb * (unsigned)(d.nT * d.Nr)), dim3(256), 0, s, d, p, f, iterPtr);
-  } else if (ringDone) {
+  } else if (ring) {
     const hipError_t e = launch_phys_ring(d, p, f, iterPtr, s);
     if (e != hipSuccess) return e;
-    *ringDone = true;
   } else
     hipLaunchKernelGGL(k_oceanic_phys, dim3(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr)), dim3(MG_PLANE_THREADS), 0, s, d, p,
                        f, iterPtr);

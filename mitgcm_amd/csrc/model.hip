@@ -56,8 +56,6 @@ hipError_t launch_mom_step(const Dims &, const Params &, const Fields &, const i
 bool mom_ring_separable(const Dims &, const Params &);
 hipError_t launch_mom_ring(const Dims &, const Params &, const Fields &, const int *, hipStream_t);
 hipError_t launch_phi_hyd(const Dims &, const Params &, const Fields &, hipStream_t);
-bool phys_phi_fusable(const Dims &, const Params &);
-hipError_t launch_phys_phi(const Dims &, const Params &, const Fields &, const int *, hipStream_t);
 hipError_t launch_sfp_rhs(const Dims &, const Params &, const Fields &, hipStream_t);
 hipError_t launch_exchange(const Dims &, double *, const long *, int, int, hipStream_t);
 hipError_t launch_cgd(const Dims &, const Params &, const Fields &, int, double, double *, hipStream_t);
@@ -85,8 +83,9 @@ hipError_t launch_update_r_star_cg2d(const Dims &, const Params &, const Fields 
                                      bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr,
                                      bool keepFac = false);
 hipError_t launch_halo_pack(const Dims &, const XFields &, const long *, long, double *, int, hipStream_t);
+bool phys_ring_ok(const Dims &, const Params &, const Fields &);
 hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
-                               bool *ringDone = nullptr);
+                               bool ring = false);
 hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, const TracerArgs &, const int *, hipStream_t,
                               bool impl = true);
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
@@ -98,8 +97,6 @@ hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, c
                                  int *, hipStream_t, int fromX, int empNext);
 bool dyn_thermo_takes_gm(const Params &);
 hipError_t launch_gm_tensor(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_hfac_snapshot(const Dims &, const Fields &, double *, hipStream_t);
-Fields hfac_snapshot_fields(const Dims &, const Fields &, double *);
 bool gm_phi_fusable(const Dims &, const Params &);
 hipError_t launch_gm_phi(const Dims &, const Params &, const Fields &, hipStream_t, bool op = false);
 bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
@@ -187,6 +184,9 @@ enum Kern { K_MOM, K_RHS, K_CG2D, K_EXCH, K_ETA, K_CORR, K_CONT, K_PHYS, K_TEMP,
 static const char *KNAMES[K_N] = {"mom_step",   "sfp_rhs",    "cg2d",         "exchange",  "eta_update",
                                   "correction", "continuity", "oceanic_phys", "temp_step", "r_star", "phi_hyd"};
 
+// the step sequences that are captured into graphs (model.hip STEP_SEQS)
+enum StepSeq { SEQ_PLAIN2 = 0, SEQ_HOIST2, SEQ_HOIST_LAST, SEQ_PLAIN1, SEQ_LAST1, SEQ_N };
+
 struct mgcm_model {
   Dims d{};
   Params p{};
@@ -198,10 +198,6 @@ struct mgcm_model {
   // DO_OCEANIC_PHYS, join before UPDATE_R_STAR / SOLVE_FOR_PRESSURE; MGCM_NO_OVERLAP=1 off)
   hipStream_t stream2 = nullptr;
   hipEvent_t evFork = nullptr, evJoin = nullptr;
-  hipEvent_t evSnap = nullptr;   // the hFac snapshot of THERMODYNAMICS beside the solve under r* (MG_FUSE_TCG)
-  double *snapH = nullptr;        // hFacC, hFacW, hFacS, recip_hFacC, recip_hFacW, recip_hFacS (6 x N3all)
-  hipStream_t stream3 = nullptr;                  // EXCH(cg2d_x) + etaN beside the correction step
-  hipEvent_t evEta0 = nullptr, evEta1 = nullptr;
   hipEvent_t evHand = nullptr;   // mgcm_stream_handoff
   bool overlap = true;
   std::vector<void *> allocs;
@@ -232,7 +228,6 @@ struct mgcm_model {
   int *d_blkx = nullptr;
   int nBlkX = 0;
   int bxyVar = -1;              // k_cg2d_bxy geometry (kernels_solve.hip CGX[])
-  int *d_slot2 = nullptr;       // per 2-D point: k_cg2d_bxy's LDS slot of its value after EXCH, or -1
   // land-block compaction of the k_cg2d_bxy tables (choose_bxy): the 2-D offsets of the points
   // of the all-land blocks left out, which the solver's prologue scans for a non-zero; empty
   // under every other solver, so the land guards do nothing there
@@ -270,15 +265,16 @@ struct mgcm_model {
   // device scratch of mgcm_exchange_host (EXCH_*_RL on caller arrays)
   double *exchBuf[2] = {nullptr, nullptr};
   long exchCap = 0;
-  // hipGraphs of two FORWARD_STEPs, one per theta/salt ping-pong parity
+  // hipGraphs of FORWARD_STEP sequences (step_graph)
   bool useGraph = true;
-  // [THERMODYNAMICS overlap off/on][tracer buffer parity][step modes: 0 plain, plain; 1 hoist, hoist; 2 hoist, last]
-  // (parity: bit 0 theta, 1 salt, 2 the passive tracers)
-  hipGraphExec_t graphExec[2][8][3] = {};
-  // ONE step (callers that step one at a time: the Fortran drop-ins) [..][..][step mode: 0 plain, 1 last]
-  hipGraphExec_t graph1Exec[2][8][2] = {};
-  double *graph1Tr[2][8][2][4] = {};     // its tracer pointers after the step: theta, thetaNext, salt, saltNext
-  bool graph1Flip[2][8][2] = {};         // ... and the passive tracers' parity after it
+  struct StepGraph {
+    hipGraphExec_t exec = nullptr;
+    double *tr[4] = {};   // the tracer pointers after the sequence: theta, thetaNext, salt, saltNext
+    int flip = 0;         // ... the passive tracers' parity after it
+    int layout = 0;       // ... and the launch layout it runs (stepLayout)
+  };
+  // [THERMODYNAMICS overlap off/on][tracer buffer parity: bit 0 theta, 1 salt, 2 the passive tracers][StepSeq]
+  StepGraph graphs[2][8][SEQ_N];
   // overlap auto-selection (ovl_trial): both graphs timed on a copy of the state
   bool ovlAuto = false, ovlDecided = false;
   float ovlMs[2] = {0.f, 0.f};
@@ -570,8 +566,7 @@ static int build_block(mgcm_model *m) {
 // column with all four faces closed at every level -- decided from the static arrays
 // INI_CG2D / UPDATE_CG2D build aW2d / aS2d from (h0FacW / h0FacS under the non-linear free
 // surface, else hFacW / hFacS) and from hFacC.  Only the kept blocks are numbered; a left-out
-// point's slot is the ZERO slot, so its neighbours read 0.0, and its slot2 is -1, so the
-// fused epilogue keeps its global value.  This is exact, not approximate, while cg2d_b and
+// point's slot is the ZERO slot, so its neighbours read 0.0.  This is exact, not approximate, while cg2d_b and
 // the first guess cg2d_x are 0.0 on those points, which holds by induction over the steps:
 //   * cg2d_b: sfp_rhs_column (common.h) sums the fluxes through the point's faces, all 0.0
 //     with the faces closed, the fresh-water term, masked by maskInC (0 on a dry column),
@@ -749,19 +744,7 @@ static int build_bxy(mgcm_model *m, const BxyChoice &c) {
       for (int k = 0; k < NB / 2; k++) nbx[(size_t)(NB / 2) * q + k] = v[2 * k] | (v[2 * k + 1] << 16);
       q++;
     }
-  // the epilogue's EXCH_XY_RL(cg2d_x): every 2-D point's value is the slot of itself
-  // (interior) or of its interior source (halo), -1 where neither (kept as it is)
-  std::vector<int> slot2((size_t)d.n2 * d.nTiles, -1);
-  for (int J = 1; J <= Ny; J++)
-    for (int I = 1; I <= Nx; I++) {
-      int i, j, t;
-      tile_point(d, I, J, i, j, t);
-      const unsigned sl = slotOf[compact(i, j, t)];
-      slot2[(size_t)MG_I2(d, i, j, t)] = sl == Z ? -1 : (int)sl;   // -1: a point of a left-out block
-    }
-  for (size_t g = 0; g < slot2.size(); g++)
-    if (srcOf[g] >= 0) slot2[g] = slot2[(size_t)srcOf[g]];
-  if (table_upload(m->d_slot2, slot2) || table_upload(m->d_nbx, nbx) || table_upload(m->d_blkx, blkx)) return -1;
+  if (table_upload(m->d_nbx, nbx) || table_upload(m->d_blkx, blkx)) return -1;
   m->bxyVar = c.var;
   m->nBlkX = c.nBlk;
   if (!m->h_dropG.empty()) {
@@ -1008,11 +991,7 @@ mgcm_model *mgcm_create(int sNx, int sNy, int OLx, int OLy, int Nr, int nSx, int
   if (hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&m->evFork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&m->evHand, hipEventDisableTiming) != hipSuccess ||
-      hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&m->evEta0, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&m->evEta1, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&m->evJoin, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&m->evSnap, hipEventDisableTiming) != hipSuccess ||
       hipEventCreate(&m->ovlEv[0]) != hipSuccess || hipEventCreate(&m->ovlEv[1]) != hipSuccess) {
     set_err("mgcm_create: second stream / events");
     delete m;
@@ -1091,7 +1070,6 @@ void mgcm_destroy(mgcm_model *m) {
   if (m->d_gofs) hipFree(m->d_gofs);
   if (m->d_nbx) hipFree(m->d_nbx);
   if (m->d_blkx) hipFree(m->d_blkx);
-  if (m->d_slot2) hipFree(m->d_slot2);
   if (m->d_dropG) hipFree(m->d_dropG);
   if (m->h_guard) hipHostFree(m->h_guard);
   if (m->d_ctr) hipFree(m->d_ctr);
@@ -1110,11 +1088,7 @@ void mgcm_destroy(mgcm_model *m) {
   if (m->ownStream) hipStreamDestroy(m->ownStream);
   if (m->stream2) hipStreamDestroy(m->stream2);
   if (m->evFork) hipEventDestroy(m->evFork);
-  if (m->evSnap) hipEventDestroy(m->evSnap);
   if (m->evHand) hipEventDestroy(m->evHand);
-  if (m->stream3) hipStreamDestroy(m->stream3);
-  if (m->evEta0) hipEventDestroy(m->evEta0);
-  if (m->evEta1) hipEventDestroy(m->evEta1);
   if (m->evJoin) hipEventDestroy(m->evJoin);
   for (auto &ev : m->ovlEv)
     if (ev) hipEventDestroy(ev);
@@ -1196,9 +1170,7 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
   if (!strcmp(name, "ovlMsOff")) return m->ovlMs[0];
   if (!strcmp(name, "cg2dBxyVariant")) return (double)m->bxyVar;
   if (!strcmp(name, "cg2dDroppedBlocks")) return (double)(m->solver == Cg2dSolver::Bxy ? m->nDropBlk : 0);
-  // the launch layout of the last FORWARD_STEP built (one_step): bit 0 THERMODYNAMICS folded
-  // into DYNAMICS' grids (k_dt_l1/l2/l3), 1 DO_OCEANIC_PHYS + CALC_PHI_HYD in one pass,
-  // 2 the tracers on the second stream, 3 joined only before the correction step
+  // the launch layout of the last FORWARD_STEP run (step_layout_bits of its plan)
   if (!strcmp(name, "stepLayout")) return (double)m->stepLayout;
   // whether the selected kernel solves with fused multiply-adds (k_cg2d_bxy honours cg2dUseFMA)
   if (!strcmp(name, "cg2dFMA")) return (m->solver == Cg2dSolver::Bxy && m->p.cg2dUseFMA) ? 1.0 : 0.0;
@@ -1501,12 +1473,11 @@ static hipError_t update_r_star_cg2d(mgcm_model *m, bool sfp = false, bool opEar
 int mgcm_init(mgcm_model *m) {
   auto ext = [&](const char *n, double dflt) { auto it = m->extra.find(n); return it == m->extra.end() ? dflt : it->second; };
   HIPCHK(hipSetDevice(m->device));
-  // the hFac snapshot THERMODYNAMICS reads beside the pressure solve under r* (one_step)
-  if (!m->snapH && m->p.nonlinFreeSurf > 0 && m->p.select_rStar > 0 &&
-      (m->p.tempStepping || m->p.saltStepping || !m->ptr.empty())) {
-    HIPCHK(hipMalloc(&m->snapH, 6 * (size_t)m->d.N3all * sizeof(double)));
-    m->allocs.push_back(m->snapH);
-  }
+  // a retired fusion bit is refused, never ignored: an A/B run must measure what it asked for
+  const char *retired = nullptr;
+  if (const int bit = mg_fuse_retired(&retired))
+    return set_err("mgcm_init: MGCM_STEP_FUSE bit %d (%s) was measured slower than the default and removed in round 10 "
+                   "(common.h); unset it", bit, retired);
   if (upload_halo(m)) return -1;
   // The CG2D solver, selected here and nowhere else:
   //   * cg2dRefOrder (parity runs on the reference's own tiling): the reference's summation
@@ -1671,18 +1642,12 @@ int mgcm_init(mgcm_model *m) {
   return 0;
 }
 
-// EXCH_XY_RL(cg2d_x) + etaN (k_exch_eta) inside the CG2D launch: the single-workgroup
-// blocked solver holds the whole solution, so its epilogue writes every point's value
-static bool cg2d_fuses_eta(const mgcm_model *m) {
-  return m->solver == Cg2dSolver::Bxy && m->d.nT == m->d.nTiles;
-}
-
-static hipError_t launch_cg2d(mgcm_model *m, int maxIters, int nIterMin, bool fuseEta = false) {
+static hipError_t launch_cg2d(mgcm_model *m, int maxIters, int nIterMin) {
   switch (m->solver) {
     case Cg2dSolver::Bxy:
       return launch_cg2d_bxy(m->bxyVar, m->d, m->p, m->f, m->d_nbx, m->d_blkx, m->nBlkX, maxIters, nIterMin, m->d_rec,
-                             m->d_ctr + 1, fuseEta ? m->d_slot2 : nullptr, m->d_srcOf, m->d_dropG, (int)m->h_dropG.size(),
-                             m->h_dropG.empty() ? nullptr : m->d_guard, m->stream);
+                             m->d_ctr + 1, m->d_dropG, (int)m->h_dropG.size(), m->h_dropG.empty() ? nullptr : m->d_guard,
+                             m->stream);
     case Cg2dSolver::BlockRef:
       return launch_cg2d_block(m->d, m->p, m->f, m->d_nbr, m->d_gofs, m->nPts, maxIters, nIterMin, m->d_rec, m->d_ctr + 1,
                                m->stream);
@@ -1752,7 +1717,7 @@ int mgcm_dynamics(mgcm_model *m) {
   return dynamics_on(m, true);
 }
 
-static TracerArgs tracer_args(mgcm_model *m, bool salt) {
+static TracerArgs tracer_args(const mgcm_model *m, bool salt) {
   const Params &p = m->p;
   TracerArgs a{};
   const int scheme = salt ? p.saltAdvScheme : p.tempAdvScheme;
@@ -1862,19 +1827,19 @@ static int ptr_tables_sync(mgcm_model *m) {
 // DO_FIELDS_BLOCKING_EXCHANGES right behind it on the same stream (nothing reads the new
 // tracers before the next step, so the end-of-step kernels stay as they are); then all pairs
 // swap together (CYCLE_TRACER)
-static int ptracers_on(mgcm_model *m, hipStream_t st, const Fields &F) {
+static int ptracers_on(mgcm_model *m, hipStream_t st) {
   const int n = (int)m->ptr.size();
   if (!n) return 0;
   if (m->ptrTabDirty) return set_err("ptracers_on: the passive tracers' device table is stale");
   if (ptr_batched(m)) {
-    TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, F, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
+    TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
                                         m->ptrNGM, m->d_ctr, st));
   } else {
     for (int i = 0; i < n; i++) {
       const TracerArgs a = tracer_args_ptr(m, i, m->ptrFlip);
       Params pp = m->p;
       pp.useGMRedi = a.gm;
-      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(F, a), a, m->d_ctr, st));
+      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st));
     }
   }
   for (int i0 = 0; i0 < n; i0 += MG_XMAX) {
@@ -1887,24 +1852,23 @@ static int ptracers_on(mgcm_model *m, hipStream_t st, const Fields &F) {
 }
 
 // TEMP_INTEGRATE / SALT_INTEGRATE (and PTRACERS_INTEGRATE) on stream `st` (the ping-pong swaps are host-side)
-static int tracers_on(mgcm_model *m, hipStream_t st, const Fields *fo = nullptr) {
+static int tracers_on(mgcm_model *m, hipStream_t st) {
   const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
-  const Fields &F = fo ? *fo : m->f;   // the fields the kernels read (fo: the hFac snapshot)
   if (tracer_hpair_ok(m->d, m->p, aT, aS)) {   // small grids: both tracers per launch
-    TIMED(K_TEMP, launch_tracer_hpair(m->d, m->p, F, aT, aS, m->d_ctr, st));
+    TIMED(K_TEMP, launch_tracer_hpair(m->d, m->p, m->f, aT, aS, m->d_ctr, st));
     std::swap(m->f.theta, m->f.thetaNext);
     std::swap(m->f.salt, m->f.saltNext);
-    return ptracers_on(m, st, F);
+    return ptracers_on(m, st);
   }
   if (m->p.tempStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, F, tracer_args(m, false), m->d_ctr, st));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, tracer_args(m, false), m->d_ctr, st));
     std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new theta is the other buffer
   }
   if (m->p.saltStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, F, tracer_args(m, true), m->d_ctr, st));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, tracer_args(m, true), m->d_ctr, st));
     std::swap(m->f.salt, m->f.saltNext);
   }
-  return ptracers_on(m, st, F);
+  return ptracers_on(m, st);
 }
 
 int mgcm_thermodynamics(mgcm_model *m) {
@@ -2079,7 +2043,7 @@ static XFields blocking_fields(const mgcm_model *m, int tracers, bool totPhi) {
 // correction+continuity, EXCH(eta)+UPDATE_ETAH, and every blocking exchange plus
 // the counter bump in one launch.  Same arithmetic as the separate C-ABI ops.
 //
-// The pipelined step (MG_FUSE_PIPE, step_pipelinable): DO_OCEANIC_PHYS and GMREDI_CALC_TENSOR
+// The pipelined step (MG_FUSE_PIPE, StepPlan::pipeOk): DO_OCEANIC_PHYS and GMREDI_CALC_TENSOR
 // of a step read only the new theta and salt, totPhiHyd, the surface hFacC and EmPmR of the
 // step before it -- nothing its pressure solve, correction step, CALC_R_STAR or velocity
 // exchange produce -- so the step before runs them in two of its own grids, which are far from
@@ -2089,7 +2053,7 @@ static XFields blocking_fields(const mgcm_model *m, int tracers, bool totPhi) {
 // for the first step of a call (so a put between calls is honoured) and leaves the last step
 // without the riders, so after a call every field holds what the plain steps leave.
 //
-// With MG_FUSE_PHIP (step_phi_pipelinable) the next step's CALC_PHI_HYD and del2uv -- the first
+// With MG_FUSE_PHIP (StepPlan::phiPipe) the next step's CALC_PHI_HYD and del2uv -- the first
 // of DYNAMICS' grids, which from the step before needs only its last launch's halos of u, v and
 // r* factors -- run in that last launch too (kernels_step.hip k_rstar_exch_phi), and the step
 // starts at the momentum grid: six launches.  The head of a call then runs that grid stand-alone
@@ -2104,43 +2068,25 @@ enum StepMode {
 // MG_FUSE_PHIP three launches, and every step saves two: the same threshold, a call of 3 gains
 // less than three times what two processes differ by (profiles/r08/step_pipeline_phi/threshold.md)
 #define MG_PIPE_MIN_STEPS 4
-// where the substitutions of the hoisted pass are exact (phys.h) and its host grids run
-static bool step_pipelinable(mgcm_model *m) {
-  const Params &p = m->p;
-  const bool tracers = p.tempStepping && p.saltStepping;
-  const bool stagger = p.staggerTimeStep != 0 && p.momStepping;
-  if (stagger || !m->overlap || !p.momStepping || !tracers || !mg_fuse_on(MG_FUSE_PIPE)) return false;
-  if (p.nonlinFreeSurf <= 0 || p.select_rStar <= 0 || !p.useRealFreshWaterFlux || !p.exactConserv) return false;
-  if (m->d.nT != m->d.nTiles || m->uvMap || !m->d_srcOf) return false;
-  if (p.nonlinFreeSurf > 0 && p.select_rStar > 0 && m->snapH && mg_fuse_on(MG_FUSE_TCG)) return false;
-  const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
-  if (!dyn_thermo_fusable(m->d, p, aT, aS) || !dyn_thermo_takes_gm(p) || phys_phi_fusable(m->d, p)) return false;
-  // the r* pass with the right-hand side and CALC_R_STAR + the exchanges: the grids that carry the riders
-  if (!mg_fuse_on(MG_FUSE_SFP) || !mg_hfuse(MG_FUSE_END, m->d.nx, m->d.ny, m->d.nT, m->d.Nr)) return false;
-  // (JMD95P reads totPhiHyd's halo: exact at the exchange source only where it is exchanged)
-  if (p.eosType == 1 && p.selectP_inEOS_Zc == 2 && !p.storePhiHyd4Phys) return false;
-  return true;
-}
-// ... and where CALC_PHI_HYD and del2uv of the next step ride in the step's last grid as well
-static bool step_phi_pipelinable(mgcm_model *m) {
-  return step_pipelinable(m) && phi_pipe_ok(m->d, m->p);
-}
-static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
-  const bool pipe = mode != STEP_PLAIN, hoist = mode == STEP_HOIST;
-  if (pipe && !step_pipelinable(m)) return set_err("one_step: the pipelined step does not apply to this model");
-  // (its own CALC_PHI_HYD + del2uv are already done; a hoisting step runs the next step's)
-  const bool phiPipe = pipe && step_phi_pipelinable(m);
+
+// The launch plan of one FORWARD_STEP: every layout decision of the step, made in plan_step
+// from the model's parameters and the MGCM_STEP_FUSE mask and nowhere else.  one_step executes
+// it; mgcm_forward_step, mgcm_prepare, ovl_trial and mgcm_step_phase read the same plan.
+struct StepPlan {
+  bool mom, rstar;   // momStepping; the non-linear free surface (r*)
+  // staggerTimeStep (forward_step.F:1003-1036): THERMODYNAMICS after the pressure solve and
+  // continuity, with the new velocities; DO_OCEANIC_PHYS still opens the step
+  bool stagger;
+  bool tracers;   // theta, salt or passive tracers are stepped
   // THERMODYNAMICS reads u, v, w, hFac and DO_OCEANIC_PHYS's outputs and writes only the
   // tracers' other buffers and AB histories; DYNAMICS reads none of those.  So once
   // DO_OCEANIC_PHYS is done the two run concurrently (second stream), joined before
   // UPDATE_R_STAR / SOLVE_FOR_PRESSURE (which rewrite hFac, then u, v, w).
-  // staggerTimeStep (forward_step.F:1003-1036): THERMODYNAMICS after the pressure solve and
-  // continuity, with the new velocities; DO_OCEANIC_PHYS still opens the step
-  const bool stagger = m->p.staggerTimeStep != 0 && m->p.momStepping;
-  const bool tracers = m->p.tempStepping || m->p.saltStepping || !m->ptr.empty();
-  const bool fork = !stagger && m->overlap && !m->timing && m->p.momStepping && tracers;
-  bool endFused = false;   // CALC_R_STAR + blocking exchanges in one launch (below)
-  bool stagEx = false;     // CALC_R_STAR + the staggered exchanges in one launch (below)
+  // canFork: the step has something to fork (ovl_trial: something to choose); forkable: and the
+  // overlap is on (decided without the timing switch: one stream, so the eager timed pass runs
+  // the layout the graph replays -- bench.py's per-kernel times and PMC attribution then
+  // describe it); fork: the second stream is really used
+  bool canFork, forkable, fork;
   // Under the linear free surface nothing between DYNAMICS and the correction step touches
   // what THERMODYNAMICS reads or writes (no r* rewrite of hFac; SOLVE_FOR_PRESSURE and CG2D
   // read gU, gV, hFac and eta, write the solver's vectors and etaN), so the tracers may run
@@ -2149,200 +2095,204 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   // idle while DYNAMICS and CALC_DIV_GHAT, alone, have the chip), under the linear free
   // surface only.  LLC-90 round 3 (profiles/r03/thermo_at/): 1.98 ms forked after
   // DO_OCEANIC_PHYS, 1.86 after DYNAMICS, 1.88 after CALC_DIV_GHAT; round 5, with the faster
-  // solve, after CALC_DIV_GHAT wins (below)
-  const bool lateJoin = fork && m->p.nonlinFreeSurf <= 0;
-  const bool thermoLate = lateJoin;
+  // solve, after CALC_DIV_GHAT wins: THERMODYNAMICS beside the CG2D only, CALC_DIV_GHAT (an HBM
+  // stream, on the critical path) alone before it -- LLC-90 1.528-1.532 -> 1.474-1.476 ms/step,
+  // alternating on one box (profiles/r05/thermo_at/); the tracers still finish inside the solve.
+  // forkLate: where a fork of this model goes (the tile-sharded driver forks there too);
+  // thermoLate: this step forks there; forkEarly: it forks right after DO_OCEANIC_PHYS and
+  // joins before UPDATE_R_STAR; thermoInline: the tracers on the model's stream, after
+  // DO_OCEANIC_PHYS (nothing forks, folds or staggers)
+  bool forkLate, thermoLate, forkEarly, thermoInline;
   // With the late join (THERMODYNAMICS beside the pressure solve) the new tracers' halos are
   // filled on the tracers' stream right after them -- DO_FIELDS_BLOCKING_EXCHANGES' theta and
   // salt, which nothing before it reads -- so the end-of-step exchange carries only the
   // velocities (MG_FUSE_TREX)
-  const bool trEx = lateJoin && mg_fuse_on(MG_FUSE_TREX);
+  bool trEx;
   // the VI path's halo-ring AB2 (launch_mom_ring) on the tracers' stream with them, when they
-  // fork right after DYNAMICS (MG_FUSE_RING; joined with them before the correction step)
-  const bool ringAside = thermoLate && mom_ring_separable(m->d, m->p) && mg_fuse_on(MG_FUSE_RING);
-  auto fork_thermo = [&]() -> int {
-    HIPCHK(hipEventRecord(m->evFork, m->stream));
-    HIPCHK(hipStreamWaitEvent(m->stream2, m->evFork, 0));
-    if (ringAside) HIPCHK(launch_mom_ring(m->d, m->p, m->f, m->d_ctr, m->stream2));
-    if (tracers_on(m, m->stream2)) return -1;
-    if (trEx) {
-      const XFields xt = blocking_fields(m, 2);
-      if (xt.n > 0) HIPCHK(launch_exchange_multi(m->d, xt, m->d_halo, m->nHalo, nullptr, m->stream2));
-    }
-    HIPCHK(hipEventRecord(m->evJoin, m->stream2));
-    return 0;
-  };
+  // fork right after DYNAMICS (MG_FUSE_RING; joined with them before the correction step).
+  // ringLate: a late fork of this model takes the ring; ringAside: this step's does
+  bool ringLate, ringAside;
   // Early fork on a small grid: THERMODYNAMICS' tracer kernels share DYNAMICS' launches
   // (kernels_step.hip, MG_FUSE_DT) instead of running on the second stream -- no fork, no join
-  const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
-  // (decided without the timing switch: one stream, so the eager timed pass runs the layout
-  // the graph replays -- bench.py's per-kernel times and PMC attribution then describe it)
-  const bool forkable = !stagger && m->overlap && m->p.momStepping && tracers;
-  // THERMODYNAMICS beside the pressure solve under r* too (MG_FUSE_TCG): UPDATE_R_STAR(.TRUE.)
-  // rewrites the hFac it reads before the solve, so it reads a copy taken on its own stream
-  // right after the fork -- the hFac of the step's start, the values FORWARD_STEP's order
-  // gives it.  DYNAMICS runs alone (no fold), UPDATE_R_STAR waits only for the copy, the
-  // correction step for the tracers.  Opt-in (MGCM_STEP_FUSE |= 512): bit-identical, but on
-  // config 2 the fold into DYNAMICS' launches stays faster, 0.2885 against 0.307 ms/step
-  // (profiles/r04/tcg/): the tracers' launches beside DYNAMICS cost more than the 190 us
-  // single-CU solve they could hide behind
-  const bool tcg = forkable && m->p.nonlinFreeSurf > 0 && m->p.select_rStar > 0 && m->snapH &&
-                   mg_fuse_on(MG_FUSE_TCG);
-  const bool tcgFork = tcg && fork;
-  const bool dtFused = forkable && !tcg && m->p.nonlinFreeSurf > 0 &&
-                       dyn_thermo_fusable(m->d, m->p, aT, aS);
-  auto fork_tcg = [&]() -> int {
-    HIPCHK(hipEventRecord(m->evFork, m->stream));
-    HIPCHK(hipStreamWaitEvent(m->stream2, m->evFork, 0));
-    HIPCHK(launch_hfac_snapshot(m->d, m->f, m->snapH, m->stream2));
-    HIPCHK(hipEventRecord(m->evSnap, m->stream2));
-    HIPCHK(launch_gm_tensor(m->d, m->p, m->f, m->stream2));
-    const Fields fT = hfac_snapshot_fields(m->d, m->f, m->snapH);
-    if (tracers_on(m, m->stream2, &fT)) return -1;
-    HIPCHK(hipEventRecord(m->evJoin, m->stream2));
-    return 0;
-  };
-  // the multi-workgroup CG2D keeps its CUs to itself while the tracers run beside it
-  m->mwg.exclusive = thermoLate ? 1 : 0;
-  // DO_OCEANIC_PHYS + DYNAMICS' CALC_PHI_HYD in one column pass where exact (phys_phi_fusable:
-  // THERMODYNAMICS, between them in FORWARD_STEP, reads DO_OCEANIC_PHYS's output and writes
-  // nothing CALC_PHI_HYD reads)
-  const bool physPhi = !stagger && m->p.momStepping && phys_phi_fusable(m->d, m->p);
-  // (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
-  m->stepLayout = (dtFused ? 1 : 0) | (physPhi ? 2 : 0) | (forkable && !dtFused ? 4 : 0) |
-                  ((forkable && m->p.nonlinFreeSurf <= 0) || tcg ? 8 : 0) | (pipe ? 16 : 0) | (phiPipe ? 32 : 0);
+  bool dtFused;
   // GMREDI_CALC_TENSOR beside CALC_PHI_HYD (launch_gm_phi) where THERMODYNAMICS, its reader,
   // runs after DYNAMICS (staggered, or forked after CALC_DIV_GHAT) and the fold does not apply
-  const bool gmPhi = (stagger || thermoLate) && !dtFused && !physPhi && !m->timing && gm_phi_fusable(m->d, m->p);
+  bool gmPhi;
+  // DO_OCEANIC_PHYS's launch runs GMREDI_CALC_TENSOR (not where launch_dyn_thermo's first grid
+  // or launch_gm_phi takes it)
+  bool physGm;
   // the VI path's halo-ring AB2 in DO_OCEANIC_PHYS's grid where it is not beside the solve
-  // (k_phys_ring, MG_FUSE_RINGP: the staggered cube)
-  bool ringPhys = false;
-  const bool ringPhysOk = !ringAside && !physPhi && mom_ring_separable(m->d, m->p) && mg_fuse_on(MG_FUSE_RINGP);
-  auto phys = [&]() -> int {
-    if (pipe) return 0;   // (done in the previous step's grids, or by mgcm_forward_step's head)
-    if (physPhi) TIMED(K_PHYS, launch_phys_phi(m->d, m->p, m->f, m->d_ctr, m->stream));
-    // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
-    else TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream,
-                                           !(dtFused && dyn_thermo_takes_gm(m->p)) && !gmPhi && !tcgFork,
-                                           ringPhysOk ? &ringPhys : nullptr));
-    return 0;
-  };
-  if (stagger || fork || dtFused) {
-    if (phys()) return -1;
-    if (tcgFork) {
-      if (fork_tcg()) return -1;
-    } else if (fork && !thermoLate && !dtFused && fork_thermo()) return -1;
-  } else {
-    if (phys() || tracers_on(m, m->stream)) return -1;
-  }
+  // (k_phys_ring, MG_FUSE_RINGP: the staggered cube; the per-point form of the launch only,
+  // phys_ring_ok); momRing: the momentum launch runs the ring itself
+  bool ringPhys, momRing;
   // UPDATE_CG2D beside DYNAMICS (ucg2d.h, MG_FUSE_OPE): the operator from h0Fac*rStarFac in
   // the fold's first grid, the preconditioner in its second; UPDATE_R_STAR then rewrites hFac only
-  const bool opEarly = dtFused && m->p.nonlinFreeSurf > 2 && dyn_thermo_takes_gm(m->p) && m->d.nT == m->d.nTiles &&
-                       mg_fuse_on(MG_FUSE_OPE);
   // (round 4 measured the operator also in GMREDI_CALC_TENSOR + CALC_PHI_HYD's grid on the
   // staggered cube: slower, 0.4235-0.4257 against 0.4165-0.4234 ms/step, profiles/r04/ope_cs/;
   // removed in round 5)
-  if (m->p.momStepping) {
-    if (dtFused) {
-      TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, aT, aS, m->d_ctr, m->stream, opEarly ? m->d_srcOf : nullptr,
-                                     !pipe, !phiPipe));
+  bool opEarly;
+  // CALC_DIV_GHAT in the r* column pass (forward_step.F:829-877: UPDATE_R_STAR(.TRUE.) +
+  // UPDATE_CG2D; MG_FUSE_SFP)
+  bool sfpFused;
+  // Under exactConserv the etaN of EXCH_XY_RL(cg2d_x) + etaN = recip_Bo*cg2d_x
+  // (solve_for_pressure.F:309-330) is read only by MOMENTUM_CORRECTION_STEP's gradient before
+  // INTEGR_CONTINUITY's EXCH(eta) + UPDATE_ETAH replaces it; k_corr_cont derives that eta from
+  // cg2d_x at the exchange sources itself.
+  // Under exactConserv nothing else reads that etaN either: INTEGR_CONTINUITY's EXCH(eta) +
+  // UPDATE_ETAH overwrites it everywhere but at points neither interior nor mapped, where it
+  // keeps recip_Bo*cg2d_x -- so with MG_FUSE_ETAX k_exch_eta is not launched at all: k_corr_cont
+  // reads eta from cg2d_x as above and the UPDATE_ETAH pass forms those points' etaN itself
+  // (fromX; cg2d_x's halo is left unexchanged: the next SOLVE_FOR_PRESSURE rewrites cg2d_x
+  // everywhere before anything reads it)
+  bool etaX;
+  // forward_step.F:965-977: CALC_R_STAR(etaH(n+1)); the next step's RESET_NLFS_VARS +
+  // UPDATE_R_STAR(.FALSE.) restore the hFac in place, so they are not repeated here.
+  // Under r* the exactConserv EXCH(eta) + UPDATE_ETAH runs inside CALC_R_STAR's pass
+  // (k_calc_r_star<FUSE>: fuseEtaH); etaHAlone: as a launch of its own (the linear free surface)
+  bool fuseEtaH, etaHAlone;
+  // CALC_R_STAR and the blocking exchanges in one grid on the small lat-lon grids
+  // (k_rstar_exch; independent, and nothing between them in the non-staggered step; MG_FUSE_END)
+  bool endFused;
+  // CALC_R_STAR + the staggered exchanges in one launch (cube/LLC maps, the whole domain:
+  // DO_STAGGER_FIELDS_EXCHANGES' u, v, w ride in CALC_R_STAR's grid, k_rstar_exmix, MG_FUSE_ENDS)
+  bool stagEx;
+  // The pipelined step.  pipeOk: the substitutions of the hoisted pass are exact (phys.h) and
+  // its host grids run -- the fold with the tensor, the r* pass with the right-hand side and
+  // CALC_R_STAR + the exchanges are the grids that carry the riders; phiPipeOk: and CALC_PHI_HYD
+  // and del2uv of the next step ride in the step's last grid as well (phi_pipe_ok).
+  // pipe / hoist: the mode asked for (StepMode); valid: it applies to this model; phiPipe: the
+  // step's own CALC_PHI_HYD + del2uv are already done; phiNext: it runs the next step's;
+  // empNext: the next step's DO_OCEANIC_PHYS left its EmPmR in EmPmRnext (rstar.h)
+  bool pipeOk, phiPipeOk, pipe, hoist, valid, phiPipe, phiNext, empNext;
+};
+static TracerArgs tracer_args(const mgcm_model *m, bool salt);
+static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
+  const Params &p = m->p;
+  const Dims &d = m->d;
+  const bool whole = d.nT == d.nTiles;   // every tile is this process's (not a tile-sharded run)
+  StepPlan pl{};
+  pl.mom = p.momStepping != 0;
+  pl.rstar = p.nonlinFreeSurf > 0;
+  pl.stagger = p.staggerTimeStep != 0 && pl.mom;
+  pl.tracers = p.tempStepping || p.saltStepping || !m->ptr.empty();
+  pl.canFork = !pl.stagger && pl.mom && pl.tracers;
+  pl.forkable = pl.canFork && m->overlap;
+  pl.fork = pl.forkable && !m->timing;
+  pl.forkLate = !pl.rstar;
+  pl.thermoLate = pl.fork && pl.forkLate;
+  pl.trEx = pl.thermoLate && mg_fuse_on(MG_FUSE_TREX);
+  const bool ringSep = mom_ring_separable(d, p);
+  pl.ringLate = pl.forkLate && ringSep && mg_fuse_on(MG_FUSE_RING);
+  pl.ringAside = pl.thermoLate && pl.ringLate;
+  pl.dtFused = pl.forkable && pl.rstar && dyn_thermo_fusable(d, p, tracer_args(m, false), tracer_args(m, true));
+  // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
+  const bool gmFold = pl.dtFused && dyn_thermo_takes_gm(p);
+  pl.forkEarly = pl.fork && !pl.thermoLate && !pl.dtFused;
+  pl.thermoInline = !pl.stagger && !pl.fork && !pl.dtFused;
+  pl.gmPhi = (pl.stagger || pl.thermoLate) && !pl.dtFused && !m->timing && gm_phi_fusable(d, p);
+  pl.physGm = !gmFold && !pl.gmPhi;
+  pl.opEarly = gmFold && p.nonlinFreeSurf > 2 && whole && mg_fuse_on(MG_FUSE_OPE);
+  pl.sfpFused = mg_fuse_on(MG_FUSE_SFP) && pl.rstar && whole;
+  pl.etaX = p.exactConserv && mg_fuse_on(MG_FUSE_ETAX) && whole;
+  pl.fuseEtaH = p.exactConserv && pl.rstar;
+  pl.etaHAlone = p.exactConserv && !pl.fuseEtaH;
+  pl.endFused = pl.mom && pl.rstar && !pl.stagger && !m->uvMap && whole && mg_hfuse(MG_FUSE_END, d.nx, d.ny, d.nT, d.Nr);
+  pl.stagEx = pl.mom && pl.rstar && !pl.endFused && pl.stagger && pl.tracers && m->uvMap && whole &&
+              mg_hfuse(MG_FUSE_ENDS, d.nx, d.ny, d.nT, d.Nr);
+  // (JMD95P reads totPhiHyd's halo: exact at the exchange source only where it is exchanged)
+  const bool totPhiHalo = p.eosType == 1 && p.selectP_inEOS_Zc == 2 && !p.storePhiHyd4Phys;
+  pl.pipeOk = gmFold && pl.sfpFused && pl.endFused && mg_fuse_on(MG_FUSE_PIPE) && p.select_rStar > 0 &&
+              p.useRealFreshWaterFlux && p.exactConserv && m->d_srcOf && !totPhiHalo;
+  pl.phiPipeOk = pl.pipeOk && phi_pipe_ok(d, p);
+  pl.pipe = mode != STEP_PLAIN;
+  pl.hoist = mode == STEP_HOIST;
+  pl.valid = !pl.pipe || pl.pipeOk;
+  pl.phiPipe = pl.pipe && pl.phiPipeOk;
+  pl.phiNext = pl.hoist && pl.phiPipe;
+  pl.empNext = pl.hoist && p.periodicExternalForcing;
+  // (a pipelined step's DO_OCEANIC_PHYS ran in the previous step's grids, or at the head of the call)
+  pl.ringPhys = !pl.pipe && !pl.ringAside && ringSep && mg_fuse_on(MG_FUSE_RINGP) && phys_ring_ok(d, p, m->f);
+  pl.momRing = !pl.ringAside && !pl.ringPhys;
+  return pl;
+}
+// mgcm_get_param("stepLayout") (model.py step_layout): bit 0 THERMODYNAMICS folded into
+// DYNAMICS' grids (k_dt_l1/l2/l3), 2 the tracers on the second stream, 3 joined only before the
+// correction step, 4 pipelined, 5 with the next step's CALC_PHI_HYD too; bit 1 is retired
+// (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
+static int step_layout_bits(const StepPlan &pl) {
+  return (pl.dtFused ? 1 : 0) | (pl.forkable && !pl.dtFused ? 4 : 0) | (pl.forkable && pl.forkLate ? 8 : 0) |
+         (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0);
+}
+
+// THERMODYNAMICS onto the second stream (after the model stream's work so far), evJoin behind
+// it; ring: the VI path's halo-ring AB2 ahead of it (StepPlan::ringAside), trEx: the new
+// tracers' halo exchange behind it (StepPlan::trEx)
+static int fork_thermo(mgcm_model *m, bool ring, bool trEx) {
+  HIPCHK(hipEventRecord(m->evFork, m->stream));
+  HIPCHK(hipStreamWaitEvent(m->stream2, m->evFork, 0));
+  if (ring) HIPCHK(launch_mom_ring(m->d, m->p, m->f, m->d_ctr, m->stream2));
+  if (tracers_on(m, m->stream2)) return -1;
+  if (trEx) {
+    const XFields xt = blocking_fields(m, 2);
+    if (xt.n > 0) HIPCHK(launch_exchange_multi(m->d, xt, m->d_halo, m->nHalo, nullptr, m->stream2));
+  }
+  HIPCHK(hipEventRecord(m->evJoin, m->stream2));
+  return 0;
+}
+
+// The executor of a StepPlan: launches, events and the CYCLE_TRACER swaps in FORWARD_STEP's order
+static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
+  const StepPlan pl = plan_step(m, mode);
+  if (!pl.valid) return set_err("one_step: the pipelined step does not apply to this model");
+  const int fromX = pl.etaX ? 1 : 0;
+  // the multi-workgroup CG2D keeps its CUs to itself while the tracers run beside it
+  m->mwg.exclusive = pl.thermoLate ? 1 : 0;
+  m->stepLayout = step_layout_bits(pl);
+  if (!pl.pipe) TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream, pl.physGm, pl.ringPhys));
+  if (pl.forkEarly && fork_thermo(m, false, false)) return -1;
+  if (pl.thermoInline && tracers_on(m, m->stream)) return -1;
+  if (pl.mom) {
+    if (pl.dtFused) {
+      TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, tracer_args(m, false), tracer_args(m, true), m->d_ctr, m->stream,
+                                     pl.opEarly ? m->d_srcOf : nullptr, !pl.pipe, !pl.phiPipe));
       std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new tracers are the other buffers
       std::swap(m->f.salt, m->f.saltNext);
       // PTRACERS_INTEGRATE where the fold replaced tracers_on: right behind it, before
       // UPDATE_R_STAR rewrites the hFac it reads
-      if (ptracers_on(m, m->stream, m->f)) return -1;
-    } else if (physPhi) TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, !ringAside && !ringPhys));
-    else if (gmPhi) {
+      if (ptracers_on(m, m->stream)) return -1;
+    } else if (pl.gmPhi) {
       TIMED(K_PHI, launch_gm_phi(m->d, m->p, m->f, m->stream));
-      TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, !ringAside && !ringPhys));
-    } else if (dynamics_on(m, !ringAside && !ringPhys)) return -1;
-    // (the late fork comes after CALC_DIV_GHAT, below)
-    if (tcgFork) HIPCHK(hipStreamWaitEvent(m->stream, m->evSnap, 0));   // the copy before hFac is rewritten
-    else if (fork && !lateJoin && !dtFused) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
-    // forward_step.F:829-877: UPDATE_R_STAR(.TRUE.) + UPDATE_CG2D
-    // (launch fusions, common.h MGCM_STEP_FUSE: CALC_DIV_GHAT in the r* column pass;
-    // EXCH(cg2d_x) + etaN in the single-workgroup CG2D's epilogue -- off by default: one CU
-    // walking every 2-D point costs more than the launch it saves)
-    const bool sfpFused = mg_fuse_on(MG_FUSE_SFP) && m->p.nonlinFreeSurf > 0 && m->d.nT == m->d.nTiles;
-    if (m->p.nonlinFreeSurf > 0)
-      TIMED(K_RSTAR, update_r_star_cg2d(m, sfpFused, opEarly, false, hoist ? m->d_ctr : nullptr, hoist && phiPipe));
-    if (!sfpFused) TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
-    // the late fork: THERMODYNAMICS beside the CG2D only, CALC_DIV_GHAT (an HBM stream, on the
-    // critical path) alone before it -- LLC-90 1.528-1.532 -> 1.474-1.476 ms/step, alternating
-    // on one box (profiles/r05/thermo_at/); the tracers still finish inside the solve
-    if (thermoLate && fork_thermo()) return -1;
-    const bool etaFused = mg_fuse_on(MG_FUSE_ETA) && cg2d_fuses_eta(m);
-    TIMED(K_CG2D, launch_cg2d(m, m->p.cg2dMaxIters, m->p.cg2dUseMinResSol - 1, etaFused));
-    // Under exactConserv the etaN of EXCH_XY_RL(cg2d_x) + etaN = recip_Bo*cg2d_x
-    // (solve_for_pressure.F:309-330) is read only by MOMENTUM_CORRECTION_STEP's gradient before
-    // INTEGR_CONTINUITY's EXCH(eta) + UPDATE_ETAH replaces it; k_corr_cont derives that eta from
-    // cg2d_x at the exchange sources itself, so k_exch_eta runs on a third stream beside it
-    // (MG_FUSE_ETAA), joined before the etaN rewrite
-    // Under exactConserv nothing else reads that etaN either: INTEGR_CONTINUITY's EXCH(eta) +
-    // UPDATE_ETAH overwrites it everywhere but at points neither interior nor mapped, where it
-    // keeps recip_Bo*cg2d_x -- so with MG_FUSE_ETAX k_exch_eta is not launched at all: k_corr_cont
-    // reads eta from cg2d_x as above and the UPDATE_ETAH pass forms those points' etaN itself
-    // (fromX; cg2d_x's halo is left unexchanged: the next SOLVE_FOR_PRESSURE rewrites cg2d_x
-    // everywhere before anything reads it)
-    const bool etaX = !etaFused && m->p.exactConserv && mg_fuse_on(MG_FUSE_ETAX) && m->d.nT == m->d.nTiles;
-    const bool etaAside = !etaX && !etaFused && m->p.exactConserv && !m->timing && mg_fuse_on(MG_FUSE_ETAA) &&
-                          m->d.nT == m->d.nTiles;
-    if (etaX) {
-    } else if (etaAside) {
-      HIPCHK(hipEventRecord(m->evEta0, m->stream));
-      HIPCHK(hipStreamWaitEvent(m->stream3, m->evEta0, 0));
-      HIPCHK(launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, false, 0, m->stream3));
-      HIPCHK(hipEventRecord(m->evEta1, m->stream3));
-    } else if (!etaFused) {
-      TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, false, 0, m->stream));
-    }
-    if (lateJoin || tcgFork) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
-    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, (etaAside || etaX) ? m->d_srcOf : nullptr, hoist));
-    if (etaAside) HIPCHK(hipStreamWaitEvent(m->stream, m->evEta1, 0));
-    // forward_step.F:965-977: CALC_R_STAR(etaH(n+1)); the next step's RESET_NLFS_VARS +
-    // UPDATE_R_STAR(.FALSE.) restore the hFac in place, so they are not repeated here.
-    // Under r* the exactConserv EXCH(eta) + UPDATE_ETAH runs inside CALC_R_STAR's pass
-    // (k_calc_r_star<FUSE>)
-    const bool fuseEtaH = m->p.exactConserv && m->p.nonlinFreeSurf > 0;
-    if (m->p.exactConserv && !fuseEtaH)
-      TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, true, 0, m->stream, etaX ? 1 : 0));
-    // CALC_R_STAR and the blocking exchanges in one grid on the small lat-lon grids
-    // (k_rstar_exch; independent, and nothing between them in the non-staggered step)
-    endFused = m->p.nonlinFreeSurf > 0 && !stagger && !m->uvMap && m->d.nT == m->d.nTiles &&
-               mg_hfuse(MG_FUSE_END, m->d.nx, m->d.ny, m->d.nT, m->d.Nr);
-    if (endFused && hoist && phiPipe) {
-      if (!fuseEtaH) return set_err("one_step: the hoisted CALC_PHI_HYD needs UPDATE_ETAH in CALC_R_STAR's pass");
+      TIMED(K_MOM, launch_mom_step(m->d, m->p, m->f, m->d_ctr, m->stream, pl.momRing));
+    } else if (dynamics_on(m, pl.momRing)) return -1;
+    if (pl.forkEarly) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
+    if (pl.rstar)
+      TIMED(K_RSTAR, update_r_star_cg2d(m, pl.sfpFused, pl.opEarly, false, pl.hoist ? m->d_ctr : nullptr, pl.phiNext));
+    if (!pl.sfpFused) TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
+    if (pl.thermoLate && fork_thermo(m, pl.ringAside, pl.trEx)) return -1;
+    TIMED(K_CG2D, launch_cg2d(m, m->p.cg2dMaxIters, m->p.cg2dUseMinResSol - 1));
+    if (!pl.etaX) TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, false, 0, m->stream));
+    if (pl.thermoLate) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
+    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, pl.etaX ? m->d_srcOf : nullptr, pl.hoist));
+    if (pl.etaHAlone) TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, true, 0, m->stream, fromX));
+    if (pl.endFused && pl.phiNext)
       TIMED(K_RSTAR, launch_rstar_exch_phi(m->d, m->p, m->f, m->d_srcOf, blocking_fields(m, 1, false), m->d_halo, m->nHalo,
-                                           m->d_ctr, m->stream, etaX ? 1 : 0, m->p.periodicExternalForcing ? 1 : 0));
-    } else if (endFused)
-      TIMED(K_RSTAR, launch_rstar_exch(m->d, m->p, m->f, m->d_srcOf, fuseEtaH, blocking_fields(m), m->d_halo, m->nHalo,
-                                       m->d_ctr, m->stream, etaX ? 1 : 0,
-                                       hoist && m->p.periodicExternalForcing ? 1 : 0));
-    else if (m->p.nonlinFreeSurf > 0) {
-      stagEx = stagger && tracers && m->uvMap && m->d.nT == m->d.nTiles &&
-               mg_hfuse(MG_FUSE_ENDS, m->d.nx, m->d.ny, m->d.nT, m->d.Nr);
-      TIMED(K_RSTAR, calc_r_star(m, fuseEtaH, etaX ? 1 : 0, stagEx));
-    }
+                                           m->d_ctr, m->stream, fromX, pl.empNext ? 1 : 0));
+    else if (pl.endFused)
+      TIMED(K_RSTAR, launch_rstar_exch(m->d, m->p, m->f, m->d_srcOf, pl.fuseEtaH, blocking_fields(m), m->d_halo, m->nHalo,
+                                       m->d_ctr, m->stream, fromX, pl.empNext ? 1 : 0));
+    else if (pl.rstar)
+      TIMED(K_RSTAR, calc_r_star(m, pl.fuseEtaH, fromX, pl.stagEx));
   } else {
     if (mgcm_integr_continuity(m)) return -1;
   }
-  if (stagger && tracers) {
-    // DO_STAGGER_FIELDS_EXCHANGES (do_stagger_fields_exchanges.F:37-43) + THERMODYNAMICS
-    if (stagEx) {     // (in CALC_R_STAR's grid, above)
-    } else if (m->uvMap) {   // u, v through the vector map and w through the scalar map, one launch
-      XFields xw{};
-      xw.p[0] = m->f.wVel; xw.nz[0] = m->d.Nr; xw.n = 1;
-      HIPCHK(uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1));
-      TIMED(K_EXCH, launch_exchange_mixed(m->d, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1], m->nUvU[1], m->nUvV[1], xw,
-                                          m->d_halo, m->nHalo, nullptr, m->stream));
-    } else {
-      TIMED(K_EXCH, exchange_uv(m, m->f.uVel, m->f.vVel, m->d.Nr, true) ? hipErrorUnknown : hipSuccess);
-      TIMED(K_EXCH, launch_exchange(m->d, m->f.wVel, m->d_halo, m->nHalo, m->d.Nr, m->stream));
-    }
+  if (pl.stagger && pl.tracers) {
+    // DO_STAGGER_FIELDS_EXCHANGES (do_stagger_fields_exchanges.F:37-43; in CALC_R_STAR's grid
+    // with stagEx) + THERMODYNAMICS
+    if (!pl.stagEx && mgcm_stagger_exchanges(m)) return -1;
     if (tracers_on(m, m->stream)) return -1;
   }
-  if (endFused) return 0;
-  const XFields xEnd = blocking_fields(m, trEx ? 0 : 1);
+  if (pl.endFused) return 0;
+  const XFields xEnd = blocking_fields(m, pl.trEx ? 0 : 1);
   if (m->uvMap) {   // the vector pair and the scalar fields in one launch
     HIPCHK(uv_pre(m, m->d, m->f.uVel, m->f.vVel, m->d.Nr, 1));
     TIMED(K_EXCH, launch_exchange_mixed(m->d, m->f.uVel, m->f.vVel, m->d.Nr, m->d_uv[1], m->nUvU[1], m->nUvV[1], xEnd,
@@ -2353,14 +2303,10 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
 }
 
 static void drop_graphs(mgcm_model *m) {
-  for (auto &row : m->graphExec)
+  for (auto &row : m->graphs)
     for (auto &col : row)
-      for (auto &ge : col)
-        if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
-  for (auto &row : m->graph1Exec)
-    for (auto &col : row)
-      for (auto &ge : col)
-        if (ge) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+      for (auto &g : col)
+        if (g.exec) { (void)hipGraphExecDestroy(g.exec); g = mgcm_model::StepGraph{}; }
 }
 
 // Which theta/salt ping-pong buffers are current (the kernels' arguments differ).
@@ -2368,56 +2314,56 @@ static int buffer_parity(const mgcm_model *m) {
   return (m->f.theta == m->thetaA ? 0 : 1) + (m->f.salt == m->saltA ? 0 : 2) + (m->ptrFlip ? 4 : 0);
 }
 
-// Two FORWARD_STEPs captured once into a hipGraph per buffer parity (the tracer
-// ping-pong swaps twice, so the pointers are back where they started), then
-// replayed: no per-kernel host launch cost inside a batch.
-// v: 0 two plain steps; 1 two pipelined steps that both hoist; 2 a hoisting step and the last
-// step of a call (StepMode)
-static int two_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
-  const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
-  if (!m->graphExec[o][q][v]) {
-    hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    int rc = one_step(m, v ? STEP_HOIST : STEP_PLAIN);
-    if (!rc) rc = one_step(m, v == 1 ? STEP_HOIST : v == 2 ? STEP_LAST : STEP_PLAIN);
-    hipError_t e = hipStreamEndCapture(m->stream, &g);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return -1; }
-    HIPCHK(e);
-    e = hipGraphInstantiate(&m->graphExec[o][q][v], g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    HIPCHK(e);
-  }
-  *out = m->graphExec[o][q][v];
-  return 0;
-}
-
-// One FORWARD_STEP captured per buffer parity (the tracer ping-pong flips it, so consecutive
-// single steps alternate between two of these graphs): a caller that steps one at a time --
-// the Fortran drop-ins, with host work between steps -- still replays instead of launching.
-// v: 0 a plain step; 1 the last step of a pipelined call
-static int one_step_graph(mgcm_model *m, hipGraphExec_t *out, int v = 0) {
-  const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
-  if (!m->graph1Exec[o][q][v]) {
-    double *pre[4] = {m->f.theta, m->f.thetaNext, m->f.salt, m->f.saltNext};
+// The step sequences replayed as hipGraphs, each captured once per THERMODYNAMICS overlap mode
+// and tracer buffer parity (mgcm_model::graphs): no per-kernel host launch cost inside a batch.
+// Two FORWARD_STEPs per graph inside a call (the tracer ping-pong swaps twice, so the pointers
+// are back where they started); ONE for the odd step of a call and for a caller that steps one
+// at a time -- the Fortran drop-ins, with host work between steps -- which still replays instead
+// of launching (the ping-pong flips the parity, so consecutive single steps alternate between
+// two of these graphs).
+static const struct { int n; StepMode mode[2]; } STEP_SEQS[SEQ_N] = {
+    {2, {STEP_PLAIN, STEP_PLAIN}},   // SEQ_PLAIN2
+    {2, {STEP_HOIST, STEP_HOIST}},   // SEQ_HOIST2: inside a pipelined call
+    {2, {STEP_HOIST, STEP_LAST}},    // SEQ_HOIST_LAST: its end
+    {1, {STEP_PLAIN, STEP_PLAIN}},   // SEQ_PLAIN1
+    {1, {STEP_LAST, STEP_LAST}},     // SEQ_LAST1: the odd last step of a pipelined call
+};
+static int step_graph(mgcm_model *m, StepSeq seq, mgcm_model::StepGraph **out = nullptr) {
+  mgcm_model::StepGraph &sg = m->graphs[m->overlap ? 1 : 0][buffer_parity(m)][seq];
+  if (!sg.exec) {
+    double **tr[4] = {&m->f.theta, &m->f.thetaNext, &m->f.salt, &m->f.saltNext};
+    double *pre[4];
+    for (int k = 0; k < 4; k++) pre[k] = *tr[k];
     const int preFlip = m->ptrFlip;
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = one_step(m, v ? STEP_LAST : STEP_PLAIN);
+    int rc = 0;
+    for (int k = 0; k < STEP_SEQS[seq].n && !rc; k++) rc = one_step(m, STEP_SEQS[seq].mode[k]);
     hipError_t e = hipStreamEndCapture(m->stream, &g);
     if (rc) { if (g) (void)hipGraphDestroy(g); return -1; }
     HIPCHK(e);
-    e = hipGraphInstantiate(&m->graph1Exec[o][q][v], g, nullptr, nullptr, 0);
+    e = hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     HIPCHK(e);
     // the capture ran one_step's host side (CYCLE_TRACER's pointer swaps) without launching:
     // keep the pointers it leaves for every replay, and undo them until the replay
-    double **tr[4] = {&m->f.theta, &m->f.thetaNext, &m->f.salt, &m->f.saltNext};
-    for (int k = 0; k < 4; k++) m->graph1Tr[o][q][v][k] = *tr[k];
-    m->f.theta = pre[0]; m->f.thetaNext = pre[1]; m->f.salt = pre[2]; m->f.saltNext = pre[3];
-    m->graph1Flip[o][q][v] = m->ptrFlip != 0;
+    for (int k = 0; k < 4; k++) { sg.tr[k] = *tr[k]; *tr[k] = pre[k]; }
+    sg.flip = m->ptrFlip;
     m->ptrFlip = preFlip;
+    sg.layout = m->stepLayout;
   }
-  *out = m->graph1Exec[o][q][v];
+  if (out) *out = &sg;
+  return 0;
+}
+// replays the sequence (captured first where it is not yet) and leaves the host side as its
+// steps would have: the tracer pointers, the passive tracers' parity, the layout it ran
+static int step_graph_launch(mgcm_model *m, StepSeq seq) {
+  mgcm_model::StepGraph *sg;
+  if (step_graph(m, seq, &sg)) return -1;
+  HIPCHK(hipGraphLaunch(sg->exec, m->stream));
+  m->f.theta = sg->tr[0]; m->f.thetaNext = sg->tr[1]; m->f.salt = sg->tr[2]; m->f.saltNext = sg->tr[3];
+  m->ptrFlip = sg->flip;
+  m->stepLayout = sg->layout;
   return 0;
 }
 int mgcm_tracer_parity(mgcm_model *m, int set) {
@@ -2434,13 +2380,6 @@ int mgcm_tracer_parity(mgcm_model *m, int set) {
   return set;
 }
 
-// after a one-step replay: the tracer pointers one_step would have left
-static void one_step_graph_done(mgcm_model *m, int o, int q, int v) {
-  m->f.theta = m->graph1Tr[o][q][v][0]; m->f.thetaNext = m->graph1Tr[o][q][v][1];
-  m->f.salt = m->graph1Tr[o][q][v][2]; m->f.saltNext = m->graph1Tr[o][q][v][3];
-  m->ptrFlip = m->graph1Flip[o][q][v] ? 1 : 0;
-}
-
 static int ovl_trial(mgcm_model *m);
 
 // Builds the graphs of the next batch and, when the THERMODYNAMICS overlap is still
@@ -2451,9 +2390,8 @@ int mgcm_prepare(mgcm_model *m) {
   if (!m->useGraph) return 0;
   HIPCHK(hipSetDevice(m->device));
   if (m->ovlAuto && !m->ovlDecided && ovl_trial(m)) return -1;
-  hipGraphExec_t ge;
-  if (step_pipelinable(m) && (two_step_graph(m, &ge, 1) || two_step_graph(m, &ge, 2))) return -1;
-  return two_step_graph(m, &ge);
+  if (plan_step(m, STEP_HOIST).valid && (step_graph(m, SEQ_HOIST2) || step_graph(m, SEQ_HOIST_LAST))) return -1;
+  return step_graph(m, SEQ_PLAIN2);
 }
 
 // THERMODYNAMICS overlap auto-selection: the device state (both field arenas, the other
@@ -2462,10 +2400,7 @@ int mgcm_prepare(mgcm_model *m) {
 // graphs each, bracketed by events -- and the state is copied back, so the caller's steps
 // are untouched; the faster graph is kept.  Both graphs compute identical results.
 static int ovl_trial(mgcm_model *m) {
-  // (one_step's `tracers`: theta, salt or passive tracers)
-  const bool forkable = !m->p.staggerTimeStep && m->p.momStepping &&
-                        (m->p.tempStepping || m->p.saltStepping || !m->ptr.empty());
-  if (!forkable) { m->ovlDecided = true; return 0; }   // one_step never forks: nothing to choose
+  if (!plan_step(m, STEP_PLAIN).canFork) { m->ovlDecided = true; return 0; }   // one_step never forks: nothing to choose
   std::vector<std::pair<void *, size_t>> parts = {
       {m->f.a2, (size_t)F2_COUNT * m->d.N2all * sizeof(double)},
       {m->f.a3, (size_t)F3_COUNT * m->d.N3all * sizeof(double)},
@@ -2496,11 +2431,10 @@ static int ovl_trial(mgcm_model *m) {
   for (int ph = 0; ph < 6 && !rc; ph++) {
     const int pairs = ph < 2 ? 1 : 2, mode = (ph & 1) ? 0 : 1;
     m->overlap = mode != 0;
-    hipGraphExec_t ge;
-    if (two_step_graph(m, &ge)) { rc = -1; break; }   // built before the events (same parity after a pair)
+    if (step_graph(m, SEQ_PLAIN2)) { rc = -1; break; }   // built before the events (same parity after a pair)
     if (hipEventRecord(m->ovlEv[0], m->stream) != hipSuccess) { rc = -1; break; }
     for (int r = 0; r < pairs && !rc; r++)
-      if (two_step_graph(m, &ge) || hipGraphLaunch(ge, m->stream) != hipSuccess) rc = -1;
+      if (step_graph_launch(m, SEQ_PLAIN2)) rc = -1;
     float ms = 0.f;
     if (rc || hipEventRecord(m->ovlEv[1], m->stream) != hipSuccess || hipEventSynchronize(m->ovlEv[1]) != hipSuccess ||
         hipEventElapsedTime(&ms, m->ovlEv[0], m->ovlEv[1]) != hipSuccess) { rc = -1; break; }
@@ -2534,32 +2468,23 @@ int mgcm_forward_step(mgcm_model *m, int nsteps) {
   // the pipelined call (one_step's StepMode): DO_OCEANIC_PHYS + GMREDI_CALC_TENSOR of the first
   // step stand-alone, from the fields as the caller left them; every step but the last then
   // runs the next step's, and the last leaves every field as the plain step does
-  const bool pipe = nsteps >= MG_PIPE_MIN_STEPS && step_pipelinable(m);
+  const StepPlan hp = plan_step(m, STEP_HOIST);
+  const bool pipe = nsteps >= MG_PIPE_MIN_STEPS && hp.valid;
   if (pipe) TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream));
   // ... and, where every step's CALC_PHI_HYD + del2uv run in the step before (MG_FUSE_PHIP), the
   // first step's: from the halos of u and v as the caller left them
-  const bool phiPipe = pipe && step_phi_pipelinable(m);
-  if (phiPipe) TIMED(K_PHI, launch_phi_del2(m->d, m->p, m->f, m->stream));
+  if (pipe && hp.phiPipe) TIMED(K_PHI, launch_phi_del2(m->d, m->p, m->f, m->stream));
   if (m->useGraph && !m->timing) {
-    for (; s + 2 <= nsteps; s += 2) {
-      hipGraphExec_t ge;
-      if (two_step_graph(m, &ge, pipe ? (s + 2 == nsteps ? 2 : 1) : 0)) return -1;
-      HIPCHK(hipGraphLaunch(ge, m->stream));
+    for (; s + 2 <= nsteps; s += 2)
+      if (step_graph_launch(m, !pipe ? SEQ_PLAIN2 : s + 2 == nsteps ? SEQ_HOIST_LAST : SEQ_HOIST2)) return -1;
+    // an odd step (a caller stepping one at a time): the one-step graph of this parity
+    if (s < nsteps) {
+      if (step_graph_launch(m, pipe ? SEQ_LAST1 : SEQ_PLAIN1)) return -1;
+      s++;
     }
-  }
-  // an odd step (a caller stepping one at a time): the one-step graph of this parity
-  if (s < nsteps && m->useGraph && !m->timing) {
-    const int q = buffer_parity(m), o = m->overlap ? 1 : 0;
-    hipGraphExec_t ge;
-    if (one_step_graph(m, &ge, pipe ? 1 : 0)) return -1;
-    HIPCHK(hipGraphLaunch(ge, m->stream));
-    one_step_graph_done(m, o, q, pipe ? 1 : 0);
-    s++;
   }
   for (; s < nsteps; s++)
     if (one_step(m, pipe ? (s == nsteps - 1 ? STEP_LAST : STEP_HOIST) : STEP_PLAIN)) return -1;
-  // (the layout this call ran, whichever graph was built last)
-  m->stepLayout = (m->stepLayout & ~48) | (pipe ? 16 : 0) | (phiPipe ? 32 : 0);
   m->lastBatch = nsteps;
   return 0;
 }
@@ -2750,15 +2675,7 @@ int mgcm_begin_steps(mgcm_model *m) {
 //   5: staggerTimeStep only: DO_STAGGER_FIELDS_EXCHANGES on this process's tiles, then
 //      THERMODYNAMICS with the new velocities;  [send/recv the 3-D halo sources again]
 //   4: DO_FIELDS_BLOCKING_EXCHANGES of this process's tiles, step counters.
-// THERMODYNAMICS onto the second stream (after the model stream's work so far) and its join
-static int shard_fork_thermo(mgcm_model *m, bool ring = false) {
-  HIPCHK(hipEventRecord(m->evFork, m->stream));
-  HIPCHK(hipStreamWaitEvent(m->stream2, m->evFork, 0));
-  if (ring) HIPCHK(launch_mom_ring(m->d, m->p, m->f, m->d_ctr, m->stream2));   // as one_step (MG_FUSE_RING)
-  if (tracers_on(m, m->stream2)) return -1;
-  HIPCHK(hipEventRecord(m->evJoin, m->stream2));
-  return 0;
-}
+// the join of THERMODYNAMICS on the second stream (fork_thermo)
 static int shard_join_thermo(mgcm_model *m) {
   if (m->shardFork == 1 || m->shardFork == 3) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
   m->shardFork = 0;
@@ -2770,20 +2687,21 @@ int mgcm_step_phase(mgcm_model *m, int phase) {
   if (check_ready(m)) return -1;
   if (!m->p.momStepping) return set_err("mgcm_step_phase: requires momStepping");
   if (!m->ptr.empty()) return set_err("mgcm_step_phase: passive tracers are not supported by the tile-sharded driver");
-  const bool stagger = m->p.staggerTimeStep != 0;
-  const bool tracers = m->p.tempStepping || m->p.saltStepping;
+  // (the resident step's plan: where it forks, the sharded step forks, whatever the overlap switch says)
+  const StepPlan pl = plan_step(m, STEP_PLAIN);
+  const bool stagger = pl.stagger;
   switch (phase) {
     case 16:  // DO_OCEANIC_PHYS, THERMODYNAMICS on the second stream as the resident step forks it
               // (one_step): beside DYNAMICS under r* (joined before UPDATE_R_STAR, which rewrites
               // hFac), beside the pressure solve under the linear free surface (forked after
               // DYNAMICS, joined before MOMENTUM_CORRECTION_STEP rewrites u, v, w)
-      if (stagger || !tracers || m->timing) {   // nothing to fork (the timed pass: one stream)
+      if (!pl.canFork || m->timing) {   // nothing to fork (the timed pass: one stream)
         phase = 8;
       } else {
         if (m->shardFork) return set_err("mgcm_step_phase(16): the previous step's THERMODYNAMICS not joined");
         TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream));
-        if (m->p.nonlinFreeSurf > 0) {
-          if (shard_fork_thermo(m)) return -1;
+        if (!pl.forkLate) {
+          if (fork_thermo(m, false, false)) return -1;
           m->shardFork = 1;
         } else {
           m->shardFork = 2;
@@ -2798,13 +2716,13 @@ int mgcm_step_phase(mgcm_model *m, int phase) {
       if (phase == 8) return 0;
       [[fallthrough]];
     case 9: {   // DYNAMICS, UPDATE_R_STAR + UPDATE_CG2D, CALC_DIV_GHAT
-      const bool ringAside = m->shardFork == 2 && mom_ring_separable(m->d, m->p) && mg_fuse_on(MG_FUSE_RING);
+      const bool ringAside = m->shardFork == 2 && pl.ringLate;
       if (dynamics_on(m, !ringAside)) return -1;
       if (m->shardFork == 1 && shard_join_thermo(m)) return -1;
       if (m->p.nonlinFreeSurf > 0) TIMED(K_RSTAR, update_r_star_cg2d(m));
       TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
       if (m->shardFork == 2) {   // after CALC_DIV_GHAT, as one_step forks it
-        if (shard_fork_thermo(m, ringAside)) return -1;
+        if (fork_thermo(m, ringAside, false)) return -1;
         m->shardFork = 3;
         m->mwg.exclusive = 1;   // the multi-workgroup CG2D keeps its CUs while the tracers run
       }

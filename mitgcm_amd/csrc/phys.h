@@ -1,7 +1,6 @@
 // phys.h -- DO_OCEANIC_PHYS's per-point work (EOS, surface forcing, IVDC), shared by
-// k_oceanic_phys (kernels_thermo.hip), the fused DO_OCEANIC_PHYS + CALC_PHI_HYD column
-// pass k_phys_phi (kernels_dyn.hip) and the next step's pass in UPDATE_R_STAR's grid
-// (kernels_rstar.hip, MG_FUSE_PIPE).
+// k_oceanic_phys (kernels_thermo.hip), k_phys_ring (kernels_dyn.hip) and the next step's pass
+// in UPDATE_R_STAR's grid (kernels_rstar.hip, MG_FUSE_PIPE).
 #pragma once
 #include "common.h"
 

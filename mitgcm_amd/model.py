@@ -285,13 +285,13 @@ class Model:
 
     def step_layout(self):
         """The launch layout of the last step built (mgcm_get_param 'stepLayout'): which
-        fusions of one_step (model.hip) the timed graph and the eager timed pass run.
+        fusions of the step's plan (model.hip plan_step) the timed graph and the eager timed pass run.
         'pipelined': the last forward_step call ran the next step's DO_OCEANIC_PHYS and
         GMREDI_CALC_TENSOR inside each step (MGCM_STEP_FUSE bit 16384; calls of 4 steps or more).
         'phi_pipelined': it also ran the next step's CALC_PHI_HYD and del2uv in each step's last
         grid (bit 32768, with 'pipelined')."""
         b = int(lib().mgcm_get_param(self.h, b"stepLayout"))
-        return {"dyn_thermo_fused": bool(b & 1), "phys_phi_fused": bool(b & 2), "thermo_second_stream": bool(b & 4),
+        return {"dyn_thermo_fused": bool(b & 1), "thermo_second_stream": bool(b & 4),
                 "late_join": bool(b & 8), "pipelined": bool(b & 16), "phi_pipelined": bool(b & 32)}
 
     def cg2d_fma(self):

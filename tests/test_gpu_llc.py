@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("march", [None, "tracer", "tracer:v1", "tracer:fwd", "tracer:fwdback", "tracer:rows", "vi",
-                                   "vi:kc3", "vi:generic", "fuse:29", "fuse:45", "fuse:77"])
+                                   "vi:kc3", "vi:generic", "fuse:77"])
 def test_llc30_8_steps_bitexact_vs_device_order_oracle(march, monkeypatch):
     """march: the LLC-90 default kernel forms forced on LLC-30 (too small to pick them by
     itself).  "tracer": the tracer right-hand side as the k-march (MGCM_TRACER_MARCH=1, five
@@ -29,9 +29,7 @@ def test_llc30_8_steps_bitexact_vs_device_order_oracle(march, monkeypatch):
     runs).  "vi": MOM_VECINV as the k-march in its compile-time specialisation
     (k_mom_vi_m2<32, 8, LLC options>; ":kc3" in chunks of 3 levels), "vi:generic" the generic k-march that serves option sets
     without an instantiation (MGCM_VI_KERNEL=march | march_generic).  "fuse:MASK": the
-    MGCM_STEP_FUSE launch fusions (29: the opt-in k_phys_phi pass; 45: the opt-in
-    EXCH(cg2d_x) + etaN beside the correction step; 77: the tracers' halo exchange on their own
-    stream)."""
+    MGCM_STEP_FUSE launch fusions (77: the tracers' halo exchange on their own stream)."""
     if march in ("tracer:fwd", "tracer:fwdback", "tracer:rows"):   # the implicit solve's forward sweep inside the
         # whole-column march, then the back substitution as a kernel of its own (2) or by the same
         # threads (3, its column pairs dealt evenly over the workgroups); "rows": (3) with whole
@@ -44,7 +42,7 @@ def test_llc30_8_steps_bitexact_vs_device_order_oracle(march, monkeypatch):
         monkeypatch.setenv("MGCM_TRACER_MARCH2", "0")
         monkeypatch.setenv("MGCM_PHYS_V2", "2")
         march = march[:-3]
-    if march and march.startswith("fuse:"):   # MGCM_STEP_FUSE mask: 29 adds DO_OCEANIC_PHYS + CALC_PHI_HYD in one pass
+    if march and march.startswith("fuse:"):   # MGCM_STEP_FUSE mask
         monkeypatch.setenv("MGCM_STEP_FUSE", march.split(":")[1])
     elif march and march.startswith("vi"):
         monkeypatch.setenv("MGCM_VI_KERNEL", "march_generic" if march.endswith("generic") else "march")

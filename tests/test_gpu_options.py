@@ -237,3 +237,36 @@ def test_unsupported_options_refused(case):
             "os7mp": "saltAdvScheme 7", "dst3_cube_ol3": "needs OLx, OLy >= 4",
             "narrow_tiles": "tiles narrower than the halo"}[case]
     assert want in msg, msg
+
+
+# MGCM_STEP_FUSE as common.h's default composes it
+STEP_FUSE_DEFAULT = 1 | 4 | 8 | 128 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768
+
+
+@pytest.mark.parametrize("bit", [2, 16, 32, 512])
+def test_retired_step_fuse_bit_refused(bit, monkeypatch):
+    """The four retired launch fusions (common.h: measured slower than the default, removed in
+    round 10): a mask that sets one is refused by mgcm_init with an error naming the bit, never
+    silently ignored, so no A/B run measures something other than what it asked for."""
+    from mitgcm_amd import configs
+    from mitgcm_amd._lib import MgcmError
+    monkeypatch.setenv("MGCM_STEP_FUSE", str(STEP_FUSE_DEFAULT | bit))
+    with pytest.raises(MgcmError, match=r"MGCM_STEP_FUSE bit %d \(" % bit):
+        configs.make_model(configs.barotropic_gyre)
+
+
+@pytest.mark.parametrize("mask", [None, STEP_FUSE_DEFAULT, STEP_FUSE_DEFAULT & ~16384])
+def test_step_fuse_masks_without_retired_bits_accepted(mask, monkeypatch):
+    """The default mask (unset and spelled out) and the default without the pipelined step still
+    create the model and take one step."""
+    from mitgcm_amd import configs
+    if mask is None:
+        monkeypatch.delenv("MGCM_STEP_FUSE", raising=False)
+    else:
+        monkeypatch.setenv("MGCM_STEP_FUSE", str(mask))
+    m = configs.make_model(configs.barotropic_gyre)
+    m.forward_step(1)
+    m.sync()
+    assert m.solve_stats()["cg2d_iters"] > 0
+    assert np.isfinite(m.get("etaN")).all()
+    m.close()
