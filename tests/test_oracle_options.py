@@ -71,3 +71,44 @@ def test_oracle_aborts_on_an_overlap_gad_check_refuses():
     bad = subprocess.run([sys.executable, "-c", prog, "3"], capture_output=True, text=True, timeout=120)
     assert bad.returncode == -6 and "stepped" not in bad.stdout, (bad.returncode, bad.stdout)
     assert "Overlap Size OLx,OLy=3 3 too small" in bad.stderr, bad.stderr
+
+
+def test_oracle_aborts_on_u3_with_one_halo_row():
+    """The same check for the U3 / C4 branches (GAD_OlMinSize 2, gad_init_fixed.F:44-49): their
+    loops 1-OLx+2 .. sNx+OLx-1 would leave the tile-edge faces 1 and sNx+1 at zero flux with
+    OL = 1.  The oracle is the reference of the passive tracers on schemes 3 and 4
+    (test_gpu_ptracers_sweep.py), so it must refuse what mgcm_init refuses: the baroclinic gyre
+    re-made with one halo row steps with scheme 2 and aborts with scheme 3; at OL = 2, the
+    experiment's own, scheme 3 steps."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prog = ("import resource, sys; sys.path.insert(0, %r)\n"
+            "resource.setrlimit(resource.RLIMIT_CORE, (0, 0))\n"
+            "import numpy as np\n"
+            "from mitgcm_amd import configs\n"
+            "from mitgcm_amd.grid import Grid\n"
+            "from oracle.harness import oracle_from_config\n"
+            "OL, scheme = int(sys.argv[1]), int(sys.argv[2])\n"
+            "def cfg():\n"
+            "    g, params, state = configs.baroclinic_gyre(nSx=1, nSy=1, tempAdvScheme=scheme)\n"
+            "    if OL == g.OLx:\n"
+            "        return g, params, state\n"
+            "    h = Grid(g.sNx, g.sNy, OL, OL, g.Nr, 1, 1)\n"
+            "    h.ini_vertical_grid(configs.BAROCLINIC_DELR)\n"
+            "    h.ini_spherical_polar_grid(np.full(62, 1.0), np.full(62, 1.0), -1.0, 14.0)\n"
+            "    h.ini_cori(selectCoriMap=2)\n"
+            "    bathy = configs.read_bin(configs.os.path.join(configs.GOLDEN, 'tutorial_baroclinic_gyre', 'bathy.bin'), (62, 62))\n"
+            "    h.ini_depths_masks(bathy, hFacMin=1.0, hFacMinDr=0.0, gBaro=9.81)\n"
+            "    h.ini_cg2d(1200.0, 1200.0, 1e-7)\n"
+            "    cut = lambda a: np.ascontiguousarray(a[..., g.OLy - OL:g.ny - g.OLy + OL, g.OLx - OL:g.nx - g.OLx + OL])\n"
+            "    return h, params, {k: (cut(v) if np.ndim(v) >= 3 else v) for k, v in state.items()}\n"
+            "o, g = oracle_from_config(cfg)\n"
+            "assert (g.OLx, g.OLy) == (OL, OL)\n"
+            "o.forward_step()\nprint('stepped')\n" % root)
+    run = lambda OL, scheme: subprocess.run([sys.executable, "-c", prog, str(OL), str(scheme)], capture_output=True,
+                                            text=True, timeout=120)
+    for OL, scheme in ((2, 3), (1, 2)):
+        ok = run(OL, scheme)
+        assert ok.returncode == 0 and "stepped" in ok.stdout, (OL, scheme, ok.stderr)
+    bad = run(1, 3)
+    assert bad.returncode == -6 and "stepped" not in bad.stdout, (bad.returncode, bad.stdout)
+    assert "Overlap Size OLx,OLy=1 1 too small: advection scheme 3 needs 2" in bad.stderr, bad.stderr
