@@ -57,6 +57,15 @@ int mgcm_exch2_maps(int sNx, int sNy, int OL, int nTiles, int ldNb, int ldT, con
 /* Run-time parameters (PARAMS.h names, already resolved as ini_parms.F does). */
 int mgcm_set_param(mgcm_model *m, const char *name, double value);
 double mgcm_get_param(mgcm_model *m, const char *name);
+/* Read-only names of mgcm_get_param beside the parameters (the model sets them, not mgcm_set_param):
+ *   ptrRoute     how the last PTRACERS_INTEGRATE issued was launched: 0 no passive tracers,
+ *                1 functional (one tracer at a time), 2 batched (MGCM_PTR_BATCH=1 where the
+ *                batched kernels apply: no k-march, and with the general form of
+ *                GAD_ADVECTION -- EXCH2 topologies, multiDimCompressible -- a halo-inclusive
+ *                tile level of at most 64 KiB in two or three fp64 arrays);
+ *   ptrLaunches  the kernel launches it took, the tracers' halo exchanges not counted.
+ * Both describe the last call that issued the tracers' launches; a replayed step graph keeps
+ * the route it was captured with. */
 
 /* The device's iteration counter (myIter: AB2's first step, the CD scheme's start),
  * written in stream order without a host synchronisation (mgcm_set_param("myIter")

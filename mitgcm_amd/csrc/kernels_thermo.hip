@@ -265,26 +265,25 @@ __device__ __forceinline__ double mask_loc(const Dims &d, const Fields &f, bool 
   return (isW ? f.maskW : f.maskS)[MG_I3(d, i, j, k, t)];
 }
 
-__global__ void __launch_bounds__(256) k_advg_init(Dims d, Fields f, TracerArgs a, int comp) {
-  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
-  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
+// The passes' arithmetic as device functions of one point of one level's frame: L (loc), V
+// (vol) and G (the face fluxes of the current stage) point at the frame's (1-OLx, 1-OLy)
+// corner, nx doubles per row -- a level of advScr1 / advScr2 / gTscr for the explicit-pass
+// kernels below, LDS for the plane kernel (k_ptr_advg_plane, kernels_ptracers.hip).  One
+// statement of the maths for both.
+#define MG_FR(d, i, j) ((i) + (d).OLx - 1 + ((j) + (d).OLy - 1) * (d).nx)
+__device__ __forceinline__ void advg_init_point(const Dims &d, const Fields &f, const TracerArgs &a, bool comp, int i, int j,
+                                                int k, int t, double *L, double *V) {
   const long q3 = MG_I3(d, i, j, k, t);
-  f.advScr1[q3] = a.tr[q3];
+  L[MG_FR(d, i, j)] = a.tr[q3];
   if (comp)
-    f.advScr2[q3] = f.rA[MG_I2(d, i, j, t)] * f.drF[k - 1] * f.hFacC[q3] + (1.0 - f.maskC[q3]);
+    V[MG_FR(d, i, j)] = f.rA[MG_I2(d, i, j, t)] * f.drF[k - 1] * f.hFacC[q3] + (1.0 - f.maskC[q3]);
 }
 
 // FILL_CS_CORNER_TR_RL(dir) on loc for the tiles whose pass calls it at this stage:
 // stage 0 X-before (X flux, overlap-only, N/S edge), 1 X-after (+ ipass = 1), 2 Y-before
-// (Y flux, overlap-only, E/W edge), 3 Y-after (+ ipass = 1); one thread per corner point
-__global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, int ipass, int stage) {
-  const int OLx = d.OLx, OLy = d.OLy, per = 4 * OLx * OLy;
-  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (long)per * d.nT * d.Nr) return;
-  const int c = (int)(g % per), z = (int)(g / per);
-  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  const int face = f.tileFace[t], edges = f.tileEdge[t];
+// (Y flux, overlap-only, E/W edge), 3 Y-after (+ ipass = 1); c: the corner point, 0..4 OLx OLy - 1
+__device__ __forceinline__ void advg_fill_point(const Dims &d, int face, int edges, int ipass, int stage, int c, double *L) {
+  const int OLx = d.OLx, OLy = d.OLy;
   const bool N = edges & 1, S = edges & 2, E = edges & 4, W = edges & 8;
   const AdvCfg cf = adv_cfg(true, face, ipass);
   bool run;
@@ -299,45 +298,41 @@ __global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, int ipass, 
   else if (corner == 1) { if (!(E && S)) return; di = sNx + ii; dj = 1 - jj; if (dir == 1) { si = sNx + jj; sj = ii; } else { si = sNx + 1 - jj; sj = 1 - ii; } }
   else if (corner == 2) { if (!(W && N)) return; di = 1 - ii; dj = sNy + jj; if (dir == 1) { si = 1 - jj; sj = sNy + 1 - ii; } else { si = jj; sj = sNy + ii; } }
   else { if (!(E && N)) return; di = sNx + ii; dj = sNy + jj; if (dir == 1) { si = sNx + jj; sj = sNy + 1 - ii; } else { si = sNx + 1 - jj; sj = sNy + ii; } }
-  f.advScr1[MG_I3(d, di, dj, k, t)] = f.advScr1[MG_I3(d, si, sj, k, t)];
+  L[MG_FR(d, di, dj)] = L[MG_FR(d, si, sj)];
 }
 
-// the X (ydir = 0) or Y (1) DST3FL face fluxes of a pass into gTscr, on the tiles that
-// compute them (GAD_DST3FL_ADV_X over i = 3-OLx..sNx+OLx-1, _Y over j = 3-OLy..sNy+OLy-1)
-__global__ void __launch_bounds__(256) k_advg_flux(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube) {
-  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
-  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
-  const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
+// the X (ydir = 0) or Y (1) DST3FL face flux of a pass into G, on the tiles that compute
+// it (GAD_DST3FL_ADV_X over i = 3-OLx..sNx+OLx-1, _Y over j = 3-OLy..sNy+OLy-1)
+__device__ __forceinline__ void advg_flux_point(const Dims &d, const Fields &f, const TracerArgs &a, int ipass, int ydir,
+                                                bool cube, int face, int edges, int i, int j, int k, int t,
+                                                const double *Lc, double *G) {
   const bool N = edges & 1, S = edges & 2, E = edges & 4, W = edges & 8;
   const AdvCfg cf = adv_cfg(cube, face, ipass);
   if (ydir ? !(cf.cy && (!cf.ov || E || W)) : !(cf.cx && (!cf.ov || N || S))) return;
-  const double *__restrict__ Lc = f.advScr1;
   const long q3 = MG_I3(d, i, j, k, t);
+  const int q = MG_FR(d, i, j);
   const double dT = a.dT, drF = f.drF[k - 1];
   double af = 0.0;
   if (!ydir && i >= 3 - d.OLx && i <= d.sNx + d.OLx - 1) {
     const double uTr = f.uVel[q3] * (f.dyG[MG_I2(d, i, j, t)] * drF * f.hFacW[q3]);
     const double cfl = fabs(f.uVel[q3] * dT * f.recip_dxC[MG_I2(d, i, j, t)]);
-    af = dst3fl_h(uTr, cfl, Lc[MG_I3(d, i - 2, j, k, t)], Lc[MG_I3(d, i - 1, j, k, t)], Lc[q3], Lc[MG_I3(d, i + 1, j, k, t)],
+    af = dst3fl_h(uTr, cfl, Lc[MG_FR(d, i - 2, j)], Lc[MG_FR(d, i - 1, j)], Lc[q], Lc[MG_FR(d, i + 1, j)],
                   mask_loc(d, f, cube, edges, true, i - 1, j, k, t), mask_loc(d, f, cube, edges, true, i, j, k, t),
                   mask_loc(d, f, cube, edges, true, i + 1, j, k, t), a.limiter);
   } else if (ydir && j >= 3 - d.OLy && j <= d.sNy + d.OLy - 1) {
     const double vTr = f.vVel[q3] * (f.dxG[MG_I2(d, i, j, t)] * drF * f.hFacS[q3]);
     const double cfl = fabs(f.vVel[q3] * dT * f.recip_dyC[MG_I2(d, i, j, t)]);
-    af = dst3fl_h(vTr, cfl, Lc[MG_I3(d, i, j - 2, k, t)], Lc[MG_I3(d, i, j - 1, k, t)], Lc[q3], Lc[MG_I3(d, i, j + 1, k, t)],
+    af = dst3fl_h(vTr, cfl, Lc[MG_FR(d, i, j - 2)], Lc[MG_FR(d, i, j - 1)], Lc[q], Lc[MG_FR(d, i, j + 1)],
                   mask_loc(d, f, cube, edges, false, i, j - 1, k, t), mask_loc(d, f, cube, edges, false, i, j, k, t),
                   mask_loc(d, f, cube, edges, false, i, j + 1, k, t), a.limiter);
   }
-  f.gTscr[q3] = af;
+  G[q] = af;
 }
 
 // the update of loc (and vol) by the X / Y flux divergence on the pass's update region
-__global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube, int comp) {
-  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
-  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
-  const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
+__device__ __forceinline__ void advg_upd_point(const Dims &d, const Fields &f, const TracerArgs &a, int ipass, int ydir,
+                                               bool cube, bool comp, int face, int edges, int i, int j, int k, int t,
+                                               double *L, double *V, const double *G) {
   const bool N = edges & 1, S = edges & 2, E = edges & 4, W = edges & 8;
   const AdvCfg cf = adv_cfg(cube, face, ipass);
   const int sNx = d.sNx, sNy = d.sNy, OLx = d.OLx, OLy = d.OLy;
@@ -363,21 +358,55 @@ __global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a
   }
   if (!upd) return;
   const long q3 = MG_I3(d, i, j, k, t), q = MG_I2(d, i, j, t);
+  const int fq = MG_FR(d, i, j), fqn = ydir ? MG_FR(d, i, j + 1) : MG_FR(d, i + 1, j);
   const double dT = a.dT, drF = f.drF[k - 1];
   const long q3n = ydir ? MG_I3(d, i, j + 1, k, t) : MG_I3(d, i + 1, j, k, t);
-  const double dF = f.gTscr[q3n] - f.gTscr[q3];
+  const double dF = G[fqn] - G[fq];
   double dU;
   if (ydir) dU = f.vVel[q3n] * (f.dxG[MG_I2(d, i, j + 1, t)] * drF * f.hFacS[q3n]) - f.vVel[q3] * (f.dxG[q] * drF * f.hFacS[q3]);
   else dU = f.uVel[q3n] * (f.dyG[MG_I2(d, i + 1, j, t)] * drF * f.hFacW[q3n]) - f.uVel[q3] * (f.dyG[q] * drF * f.hFacW[q3]);
   if (comp) {
-    const double tmpTrac = f.advScr1[q3] * f.advScr2[q3] - dT * dF * f.maskInC[q];
-    const double vol = f.advScr2[q3] - dT * dU * f.maskInC[q];
-    f.advScr2[q3] = vol;
-    f.advScr1[q3] = tmpTrac / vol;
+    const double tmpTrac = L[fq] * V[fq] - dT * dF * f.maskInC[q];
+    const double vol = V[fq] - dT * dU * f.maskInC[q];
+    V[fq] = vol;
+    L[fq] = tmpTrac / vol;
   } else {
-    f.advScr1[q3] = f.advScr1[q3] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
-                                        (dF - a.tr[q3] * dU) * f.maskInC[q];
+    L[fq] = L[fq] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] * (dF - a.tr[q3] * dU) * f.maskInC[q];
   }
+}
+
+// the explicit-pass kernels: one thread per frame point (per corner point: k_advg_fill), the
+// frames being level k of tile t of advScr1 / advScr2 / gTscr
+#define MG_LEVEL(p, d, k, t) ((p) + (long)((k) - 1) * (d).n2 + (long)(t) * (d).n3)
+__global__ void __launch_bounds__(256) k_advg_init(Dims d, Fields f, TracerArgs a, int comp) {
+  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
+  advg_init_point(d, f, a, comp != 0, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t), MG_LEVEL(f.advScr2, d, k, t));
+}
+__global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, int ipass, int stage) {
+  const int per = 4 * d.OLx * d.OLy;
+  const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long)per * d.nT * d.Nr) return;
+  const int c = (int)(g % per), z = (int)(g / per);
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  advg_fill_point(d, f.tileFace[t], f.tileEdge[t], ipass, stage, c, MG_LEVEL(f.advScr1, d, k, t));
+}
+__global__ void __launch_bounds__(256) k_advg_flux(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube) {
+  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
+  const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
+  advg_flux_point(d, f, a, ipass, ydir, cube != 0, face, edges, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t),
+                  MG_LEVEL(f.gTscr, d, k, t));
+}
+__global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube, int comp) {
+  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
+  const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
+  advg_upd_point(d, f, a, ipass, ydir, cube != 0, comp != 0, face, edges, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t),
+                 MG_LEVEL(f.advScr2, d, k, t), MG_LEVEL(f.gTscr, d, k, t));
 }
 
 // tracer_rhs_body with its operands loaded behind the reference's conditions: the form the
@@ -1304,39 +1333,42 @@ static bool tracer_march_on(const Dims &d) {
 }
 
 // impl = false: the right-hand side only (the implicit solve is launched by the caller)
+// nLaunch (or null): the kernel launches issued are added to it, counted where they are issued
 hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a, const int *iterPtr,
-                              hipStream_t s, bool impl) {
+                              hipStream_t s, bool impl, int *nLaunch) {
+  struct Count { int n, *out; ~Count() { if (out) *out += n; } } cnt{0, nLaunch};
+#define MG_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); cnt.n++; } while (0)
   const dim3 blk(MG_PLANE_THREADS), grd(mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr));
   if (a.multiDim) {
     const dim3 fgrd(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr));
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: fused per-point X and Y passes
-      hipLaunchKernelGGL(k_adv_x, fgrd, blk, 0, s, d, f, a);
-      hipLaunchKernelGGL(k_adv_y, grd, blk, 0, s, d, f, a);
-      hipLaunchKernelGGL(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr2, f.advScr2);
+      MG_LAUNCH(k_adv_x, fgrd, blk, 0, s, d, f, a);
+      MG_LAUNCH(k_adv_y, grd, blk, 0, s, d, f, a);
+      MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr2, f.advScr2);
     } else {                // the general form: explicit passes over the whole slab
-      hipLaunchKernelGGL(k_advg_init, fgrd, blk, 0, s, d, f, a, (int)comp);
+      MG_LAUNCH(k_advg_init, fgrd, blk, 0, s, d, f, a, (int)comp);
       const unsigned cgrd = (unsigned)((4L * d.OLx * d.OLy * d.nT * d.Nr + 255) / 256);
       for (int ipass = 1; ipass <= (cube ? 3 : 2); ipass++)
         for (int ydir = 0; ydir < 2; ydir++) {
-          if (cube) hipLaunchKernelGGL(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir);
-          hipLaunchKernelGGL(k_advg_flux, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube);
-          if (cube) hipLaunchKernelGGL(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir + 1);
-          hipLaunchKernelGGL(k_advg_upd, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube, (int)comp);
+          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir);
+          MG_LAUNCH(k_advg_flux, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube);
+          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir + 1);
+          MG_LAUNCH(k_advg_upd, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube, (int)comp);
         }
-      if (comp) hipLaunchKernelGGL(k_adv_r<true>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr2);
-      else hipLaunchKernelGGL(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr1);
+      if (comp) MG_LAUNCH(k_adv_r<true>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr2);
+      else MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr1);
     }
   }
   // GM/Redi fluxes as a template switch: without them the kernel holds half the registers
   // a passive tracer with forcing of its own (pkg/ptracers): the generic body's PTR form, whose
   // arithmetic is the flat and marching forms' (they are bit-identical restatements of it)
   const bool ptrForc = a.relaxRate != 0.0 || a.src != 0.0;
-  if (ptrForc && p.useGMRedi) hipLaunchKernelGGL((k_tracer_rhs<true, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
-  else if (ptrForc) hipLaunchKernelGGL((k_tracer_rhs<false, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
-  else if (p.useGMRedi) hipLaunchKernelGGL(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
+  if (ptrForc && p.useGMRedi) MG_LAUNCH((k_tracer_rhs<true, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
+  else if (ptrForc) MG_LAUNCH((k_tracer_rhs<false, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
+  else if (p.useGMRedi) MG_LAUNCH(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (a.scheme != 2 || p.useAB3)   // U3 / C4 and ADAMS_BASHFORTH3: the generic body only
-    hipLaunchKernelGGL(k_tracer_rhs<false>, grd, blk, 0, s, d, p, f, a, iterPtr);
+    MG_LAUNCH(k_tracer_rhs<false>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (tracer_march_on(d)) {
     // the k-march (deep grids; MGCM_TRACER_MARCH=0|1 overrides): KC levels per workgroup, five
     // chunks (round 3: LLC-90 fastest among 1/2/5/10 chunks, profiles/r03/)
@@ -1366,36 +1398,37 @@ hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, c
               nCU = 256;
             const long np = (long)hx * d.sNy * d.nT;
             const int pw = (int)std::min<long>(256, (np + nCU - 1) / nCU);
-            hipLaunchKernelGGL((k_tracer_march2<true, true>), dim3((unsigned)((np + pw - 1) / pw)), blk, 0, s, d, p, f, a,
+            MG_LAUNCH((k_tracer_march2<true, true>), dim3((unsigned)((np + pw - 1) / pw)), blk, 0, s, d, p, f, a,
                                iterPtr, d.Nr, 1, -pw);
             return hipGetLastError();
           }
-          hipLaunchKernelGGL((k_tracer_march2<true, true>), dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
+          MG_LAUNCH((k_tracer_march2<true, true>), dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
                              d.Nr, 1, nty2);
           return hipGetLastError();
         }
-        hipLaunchKernelGGL((k_tracer_march2<true, false>), dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
+        MG_LAUNCH((k_tracer_march2<true, false>), dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
                            d.Nr, 1, nty2);
-        hipLaunchKernelGGL(k_tracer_backsub, dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, a, nty2);
+        MG_LAUNCH(k_tracer_backsub, dim3((unsigned)(nty2 * d.nT)), blk, 0, s, d, a, nty2);
         return hipGetLastError();
       }
-      hipLaunchKernelGGL((k_tracer_march2<false, false>), dim3((unsigned)(nkc * nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
+      MG_LAUNCH((k_tracer_march2<false, false>), dim3((unsigned)(nkc * nty2 * d.nT)), blk, 0, s, d, p, f, a, iterPtr,
                          KC, nkc, nty2);
     } else
-      hipLaunchKernelGGL(k_tracer_march, dim3((unsigned)(nkc * ntx * nty * d.nT)), blk, 0, s, d, p, f, a, iterPtr, KC, nkc,
+      MG_LAUNCH(k_tracer_march, dim3((unsigned)(nkc * ntx * nty * d.nT)), blk, 0, s, d, p, f, a, iterPtr, KC, nkc,
                          ntx, nty);
-  } else hipLaunchKernelGGL(k_tracer_rhs_flat, grd, blk, 0, s, d, p, f, a, iterPtr);
+  } else MG_LAUNCH(k_tracer_rhs_flat, grd, blk, 0, s, d, p, f, a, iterPtr);
   if (p.implicitDiffusion && impl) {
     const long ncol = (long)d.sNx * d.sNy * d.nT;
     const int nc = mg_colf_nc(ncol, d.Nr, 3);
     MG_ALLOW_LDS(k_tracer_impl<false>);
     MG_ALLOW_LDS(k_tracer_impl<true>);
     if (d.Nr >= 30)
-      hipLaunchKernelGGL(k_tracer_impl<true>, dim3(mg_colf_blocks(ncol, nc)), blk, mg_colf_lds(d.Nr, nc, 3), s, d, p, f, a, nc);
+      MG_LAUNCH(k_tracer_impl<true>, dim3(mg_colf_blocks(ncol, nc)), blk, mg_colf_lds(d.Nr, nc, 3), s, d, p, f, a, nc);
     else
-      hipLaunchKernelGGL(k_tracer_impl<false>, dim3(mg_colf_blocks(ncol, nc)), blk, mg_colf_lds(d.Nr, nc, 3), s, d, p, f, a, nc);
+      MG_LAUNCH(k_tracer_impl<false>, dim3(mg_colf_blocks(ncol, nc)), blk, mg_colf_lds(d.Nr, nc, 3), s, d, p, f, a, nc);
   }
   return hipGetLastError();
+#undef MG_LAUNCH
 }
 
 }  // namespace mgcm

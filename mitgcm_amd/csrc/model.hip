@@ -87,7 +87,7 @@ bool phys_ring_ok(const Dims &, const Params &, const Fields &);
 hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
                                bool ring = false);
 hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, const TracerArgs &, const int *, hipStream_t,
-                              bool impl = true);
+                              bool impl = true, int *nLaunch = nullptr);
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
 hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
                              hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true);
@@ -103,9 +103,9 @@ bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const Tra
 hipError_t launch_tracer_hpair(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &,
                                const int *, hipStream_t);
 hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, hipStream_t);
-bool ptr_batch_ok(const Dims &, const Params &);
+bool ptr_batch_ok(const Dims &, const Params &, bool md);
 hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int, int, int,
-                                 int, const int *, hipStream_t);
+                                 int, const int *, hipStream_t, int *nLaunch = nullptr);
 }  // namespace mgcm
 
 using namespace mgcm;
@@ -281,6 +281,9 @@ struct mgcm_model {
   hipEvent_t ovlEv[2] = {nullptr, nullptr};
   double *thetaA = nullptr, *saltA = nullptr;
   int stepLayout = 0;   // one_step's launch layout (mgcm_get_param "stepLayout")
+  // the last ptracers_on (mgcm_get_param "ptrRoute", "ptrLaunches"): 0 no tracers, 1 functional, 2 batched;
+  // the kernel launches it issued for PTRACERS_INTEGRATE, the exchanges not counted
+  int ptrRoute = 0, ptrLaunches = 0;
   // pkg/ptracers (mgcm_ptracers_alloc): a third arena, sized at run time, of PTR_NF 3-D fields
   // per tracer -- the ping-pong pair, gpTrNm1 and the tracer's own T*, advScr1 (also the
   // marches' c'), advScr2 and gAdv scratch: the batched kernels run the tracers concurrently
@@ -1172,6 +1175,9 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
   if (!strcmp(name, "cg2dDroppedBlocks")) return (double)(m->solver == Cg2dSolver::Bxy ? m->nDropBlk : 0);
   // the launch layout of the last FORWARD_STEP run (step_layout_bits of its plan)
   if (!strcmp(name, "stepLayout")) return (double)m->stepLayout;
+  // the route of the last ptracers_on (0 no tracers, 1 functional, 2 batched) and its launches
+  if (!strcmp(name, "ptrRoute")) return (double)m->ptrRoute;
+  if (!strcmp(name, "ptrLaunches")) return (double)m->ptrLaunches;
   // whether the selected kernel solves with fused multiply-adds (k_cg2d_bxy honours cg2dUseFMA)
   if (!strcmp(name, "cg2dFMA")) return (m->solver == Cg2dSolver::Bxy && m->p.cg2dUseFMA) ? 1.0 : 0.0;
   for (auto &pd : PARAMS)
@@ -1775,21 +1781,28 @@ static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip) {
   a.adv1 = t.adv1; a.adv2 = t.adv2; a.gAdv = t.gAdv;
   return a;
 }
-// MGCM_PTR_BATCH=1: the batched kernels wherever they apply (kernels_ptracers.hip ptr_batch_ok,
-// lat-lon maps); =0 and the default: one launch_tracer_step per tracer.  Read whenever
+// MGCM_PTR_BATCH=1: the batched kernels wherever they apply (kernels_ptracers.hip ptr_batch_ok:
+// no k-march, no ADAMS_BASHFORTH3, and where the multi-dimensional tracers take the general form
+// of GAD_ADVECTION -- every EXCH2 topology, multiDimCompressible -- a frame of at most 64 KiB);
+// =0 and the default: one launch_tracer_step per tracer.  Read whenever
 // ptracers_on runs, which for forward_step is when a step graph is captured: the graph caches
 // are not keyed on the switch (nor on MGCM_STEP_FUSE), so a model that has captured its graphs
-// keeps their route whatever the variable says later (tools/ptracers_ab.py: one model per route).
-// The default is the measurement's (tools/ptracers_ab.py, profiles/r09/ptracers/): on
+// keeps their route whatever the variable says later (tools/ptracers_ab.py, tools/ptracers_cube_ab.py:
+// one model per route); mgcm_get_param "ptrRoute" / "ptrLaunches" say which route ran.
+// The default is the lat-lon measurement's (tools/ptracers_ab.py, profiles/r09/ptracers/): on
 // tutorial_global_oce_latlon the tracers run beside the 190 us pressure solve, where 4 tracers
 // cost nothing either way and the batched launches measured 1 % above the per-tracer ones in
 // every alternation (0.2575-0.2650 against 0.2547-0.2624 ms/step), although they take 57 us
 // of kernel time in 5 launches against 134 us in 20; at 8 tracers the per-tracer launches
 // outlast the solve (0.387 ms/step) and the batched ones do not (0.258): set it to 1 there.
+// On the cube it is the faster route from the first tracer on (tools/ptracers_cube_ab.py,
+// profiles/r11/ptracers_cube/): global_ocean.cs32x15 is staggered with r*, the tracers sit on the
+// critical path before UPDATE_R_STAR, and a scheme-33 tracer is 28 launches there: 0.519 against
+// 0.476 ms/step at 1 tracer, 0.843 against 0.485 at 4, 1.298 against 0.522 at 8 (0.391 without).
 static bool ptr_batched(const mgcm_model *m) {
   const char *e = getenv("MGCM_PTR_BATCH");
   if (!e || atoi(e) == 0) return false;
-  return !m->uvMap && ptr_batch_ok(m->d, m->p);
+  return ptr_batch_ok(m->d, m->p, m->ptrNMd > 0);
 }
 // The batched kernels' device tables, one per parity: uploaded by mgcm_init and, after a
 // parameter change, by the next entry point that steps (never inside a graph capture)
@@ -1829,17 +1842,21 @@ static int ptr_tables_sync(mgcm_model *m) {
 // swap together (CYCLE_TRACER)
 static int ptracers_on(mgcm_model *m, hipStream_t st) {
   const int n = (int)m->ptr.size();
+  m->ptrRoute = 0;
+  m->ptrLaunches = 0;
   if (!n) return 0;
   if (m->ptrTabDirty) return set_err("ptracers_on: the passive tracers' device table is stale");
   if (ptr_batched(m)) {
+    m->ptrRoute = 2;
     TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
-                                        m->ptrNGM, m->d_ctr, st));
+                                        m->ptrNGM, m->d_ctr, st, &m->ptrLaunches));
   } else {
+    m->ptrRoute = 1;
     for (int i = 0; i < n; i++) {
       const TracerArgs a = tracer_args_ptr(m, i, m->ptrFlip);
       Params pp = m->p;
       pp.useGMRedi = a.gm;
-      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st));
+      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st, true, &m->ptrLaunches));
     }
   }
   for (int i0 = 0; i0 < n; i0 += MG_XMAX) {

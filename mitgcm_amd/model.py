@@ -294,6 +294,15 @@ class Model:
         return {"dyn_thermo_fused": bool(b & 1), "thermo_second_stream": bool(b & 4),
                 "late_join": bool(b & 8), "pipelined": bool(b & 16), "phi_pipelined": bool(b & 32)}
 
+    def ptracers_route(self):
+        """How the last PTRACERS_INTEGRATE issued was launched (mgcm_get_param 'ptrRoute',
+        'ptrLaunches'): 'route' is 'none' (no passive tracers), 'functional' (one
+        launch_tracer_step per tracer) or 'batched' (MGCM_PTR_BATCH=1 where the batched kernels
+        apply: every tracer per launch); 'launches' the kernel launches it took, the halo
+        exchanges not counted.  A replayed step graph keeps the route it was captured with."""
+        r = int(lib().mgcm_get_param(self.h, b"ptrRoute"))
+        return {"route": ("none", "functional", "batched")[r], "launches": int(lib().mgcm_get_param(self.h, b"ptrLaunches"))}
+
     def cg2d_fma(self):
         """True when the selected CG2D kernel solves in fused multiply-adds (cg2dUseFMA): the
         device-order oracle must then evaluate the same fma chains (Oracle.set_sum_plan(fma=))."""
