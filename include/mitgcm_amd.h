@@ -63,9 +63,16 @@ double mgcm_get_param(mgcm_model *m, const char *name);
  *                batched kernels apply: no k-march, and with the general form of
  *                GAD_ADVECTION -- EXCH2 topologies, multiDimCompressible -- a halo-inclusive
  *                tile level of at most 64 KiB in two or three fp64 arrays);
- *   ptrLaunches  the kernel launches it took, the tracers' halo exchanges not counted.
- * Both describe the last call that issued the tracers' launches; a replayed step graph keeps
- * the route it was captured with. */
+ *   ptrLaunches  the kernel launches it took, the tracers' halo exchanges not counted;
+ *   gmResFlow    1 when the last THERMODYNAMICS issued formed GMREDI_RESIDUAL_FLOW as fields
+ *                (uRes, vRes, wRes: the Eulerian velocity plus GM_AdvForm's bolus velocity)
+ *                for GAD_ADVECTION's multi-dimensional passes: useGMRedi with GM_AdvForm and
+ *                theta, salt or a passive tracer on scheme 30 or 33; 0 otherwise (scheme-2
+ *                tracers form the bolus terms inside their right-hand side).
+ * All describe the last call that issued the tracers' launches; a replayed step graph keeps
+ * what it was captured with.
+ * GM_AdvForm is accepted with every advection scheme the device carries (2, 3, 4, 30, 33); it
+ * still needs GM_skewflx = 0 (gmredi_readparms.F:243-244), which mgcm_init checks. */
 
 /* The device's iteration counter (myIter: AB2's first step, the CD scheme's start),
  * written in stream order without a host synchronisation (mgcm_set_param("myIter")

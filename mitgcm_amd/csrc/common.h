@@ -40,7 +40,7 @@ struct Dims {
     X(gtNm1) X(thetaNext) X(gTscr) X(cpScr) X(phiHydC) X(saltNext) X(gsNm1) X(advScr1) X(advScr2) X(gAdv) \
     X(sigmaR) X(Kwx) X(Kwy) X(Kwz) X(Kux) X(Kvy) X(uVelD) X(vVelD) X(uNM1) X(vNM1) X(cdU) X(cdV) X(h0FacC) \
     X(h0FacW) X(h0FacS) X(totPhiHyd) X(alphaRho) X(del2u) X(del2v) X(dWtC) X(dWtU) X(dWtV) X(Kuz) X(Kvz) \
-    X(GM_PsiX) X(GM_PsiY) X(gtNm2) X(gsNm2)
+    X(GM_PsiX) X(GM_PsiY) X(gtNm2) X(gsNm2) X(uRes) X(vRes) X(wRes)
 #define MG_ENUM2(n) F2_##n,
 #define MG_ENUM3(n) F3_##n,
 enum F2Id { MG_F2D_LIST(MG_ENUM2) F2_COUNT };
@@ -120,6 +120,9 @@ struct Fields {
   double *Qnet, *EmPmR, *SSS, *lambdaSaltClimRelax, *etaNm1;   // 2-D
   double *sigmaR, *Kwx, *Kwy, *Kwz, *Kux, *Kvy;                // 3-D GM/Redi
   double *Kuz, *Kvz, *GM_PsiX, *GM_PsiY;                       // 3-D GM_ExtraDiag / GM_AdvForm
+  // 3-D: uFld, vFld, wFld of thermodynamics.F:252-270 under GM_AdvForm, the Eulerian velocity plus
+  // GMREDI_RESIDUAL_FLOW's bolus velocity (k_gm_residual_flow; what the multi-dimensional passes advect by)
+  double *uRes, *vRes, *wRes;
   double *uVelD, *vVelD, *uNM1, *vNM1, *cdU, *cdV;             // 3-D CD scheme (+ gUtmp/gVtmp scratch)
   // r* coordinate (global_ocean.90x40x15): rest-state hFac, column geometry, the r* factors
   const double *h0FacC, *h0FacW, *h0FacS;                                  // 3-D
@@ -381,6 +384,13 @@ struct TracerArgs {
 __host__ __device__ inline Fields ptr_fields(const Fields &f, const TracerArgs &a) {
   Fields g = f;
   g.advScr1 = a.adv1; g.advScr2 = a.adv2; g.gAdv = a.gAdv;
+  return g;
+}
+// The Fields GAD_ADVECTION's multi-dimensional passes get under GM_AdvForm: the residual flow in
+// place of the Eulerian velocity, transports and CFL numbers alike (k_gm_residual_flow has run)
+__host__ __device__ inline Fields res_flow_fields(const Fields &f) {
+  Fields g = f;
+  g.uVel = f.uRes; g.vVel = f.vRes; g.wVel = f.wRes;
   return g;
 }
 // surfaceForcingPTr of a tracer with surface relaxation (ptracers_forcing_surf.F, the

@@ -193,25 +193,28 @@ bool ptr_batch_ok(const Dims &d, const Params &p, bool md) {
 // starting at lists + stride, its first nGM tracers the ones that take GM/Redi.  nLaunch (or
 // null): the kernel launches issued are added to it.  (The lists are all the kernels know of
 // who they step: theta and salt could join one with TracerArgs of their own.)
+// resFlow: the multi-dimensional passes advect by GM_AdvForm's residual flow (launch_tracer_step)
 hipError_t launch_ptracers_batch(const Dims &d, const Params &p, const Fields &f, const TracerArgs *tab, const int *lists,
-                                 int stride, int nMd, int nAll, int nGM, const int *iterPtr, hipStream_t s, int *nLaunch) {
+                                 int stride, int nMd, int nAll, int nGM, const int *iterPtr, hipStream_t s, int *nLaunch,
+                                 bool resFlow) {
   if (nAll <= 0) return hipSuccess;
   int nl = 0;
   const dim3 blk(MG_PLANE_THREADS);
   const int nbI = (int)mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr), nbF = (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
   if (nMd > 0) {
+    const Fields fm = resFlow ? res_flow_fields(f) : f;
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: the per-point X and Y passes
-      hipLaunchKernelGGL(k_ptr_adv_x, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbF);
-      hipLaunchKernelGGL(k_ptr_adv_y, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbI);
-      hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 0);
+      hipLaunchKernelGGL(k_ptr_adv_x, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, fm, tab, lists, nMd, nbF);
+      hipLaunchKernelGGL(k_ptr_adv_y, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, fm, tab, lists, nMd, nbI);
+      hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 0);
       nl += 3;
     } else {                // the general form: every pass of a level in one workgroup
       if (ptr_plane_lds(d, p) > MG_PTR_PLANE_LDS_MAX) return hipErrorInvalidValue;   // (ptr_batch_ok was not asked)
       hipLaunchKernelGGL(k_ptr_advg_plane, dim3((unsigned)(d.nT * d.Nr * nMd)), dim3(ptr_plane_threads(d)), ptr_plane_lds(d, p), s,
-                         d, f, tab, lists, nMd, (int)cube, (int)comp);
-      if (comp) hipLaunchKernelGGL(k_ptr_adv_r<true>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
-      else hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
+                         d, fm, tab, lists, nMd, (int)cube, (int)comp);
+      if (comp) hipLaunchKernelGGL(k_ptr_adv_r<true>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 1);
+      else hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 1);
       nl += 2;
     }
   }

@@ -83,6 +83,36 @@ __global__ void __launch_bounds__(256) k_oceanic_phys2(Dims d, Params p, Fields 
 
 __global__ void __launch_bounds__(256) k_gm_tensor(Dims d, Params p, Fields f) { gm_tensor_body(d, p, f, mg_xcd_block()); }
 
+// GMREDI_RESIDUAL_FLOW (gmredi_residual_flow.F:58-97) on THERMODYNAMICS' copy of the flow
+// (thermodynamics.F:252-270): uRes, vRes, wRes = the Eulerian velocity plus the bolus velocity of
+// GM_PsiX / GM_PsiY, once per step for every tracer GAD_ADVECTION's multi-dimensional passes
+// advect.  The expressions and their order are tracer_rhs_body's uFld / vFld / wFld (the
+// scheme-2 tracers keep forming them on the fly).  One thread per (i,j,k) of the halo-inclusive
+// slab: u and v everywhere, w on 1-OL .. sN+OL-1 (it reads Psi at i+1 and j+1) and a copy of
+// wVel on the last row and column.  Psi is zero on the slab's outer ring (gm_tensor_body's range).
+__global__ void __launch_bounds__(256) k_gm_residual_flow(Dims d, Params p, Fields f) {
+  MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
+  const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
+  if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
+  const int Nr = d.Nr;
+  const int kp1 = k + 1 < Nr ? k + 1 : Nr;
+  const double maskp1 = k >= Nr ? 0.0 : 1.0;
+  const double flip = -p.gravitySign, rdr = f.recip_drF[k - 1];
+  const long q = MG_I2(d, i, j, t), q3 = MG_I3(d, i, j, k, t), q3p = MG_I3(d, i, j, kp1, t);
+  const double pxW = f.GM_PsiX[q3], pyS = f.GM_PsiY[q3];
+  double delPsi = f.GM_PsiX[q3p] * 1.0 * maskp1 - pxW * 1.0;
+  f.uRes[q3] = f.uVel[q3] + delPsi * rdr * f.recip_hFacW[q3] * 1.0 * flip;
+  delPsi = f.GM_PsiY[q3p] * 1.0 * maskp1 - pyS * 1.0;
+  f.vRes[q3] = f.vVel[q3] + delPsi * rdr * f.recip_hFacS[q3] * 1.0 * flip;
+  double w = f.wVel[q3];
+  if (i <= d.sNx + d.OLx - 1 && j <= d.sNy + d.OLy - 1) {
+    delPsi = (f.dyG[MG_I2(d, i + 1, j, t)] * f.GM_PsiX[MG_I3(d, i + 1, j, k, t)] - f.dyG[q] * pxW +
+              f.dxG[MG_I2(d, i, j + 1, t)] * f.GM_PsiY[MG_I3(d, i, j + 1, k, t)] - f.dxG[q] * pyS);
+    w = w + delPsi * f.recip_rA[q] * 1.0 * flip;
+  }
+  f.wRes[q3] = w;
+}
+
 // ---------------------------------------------------------------------------
 // GAD_DST3FL_ADV_X/Y/R (gad_dst3fl_adv_x.F:47-99, _y.F, _r.F:70-119)
 __device__ __forceinline__ double dst3fl_limit(double d0, double d1, double theta, double cfl) {
@@ -1277,6 +1307,14 @@ hipError_t launch_gm_tensor(const Dims &d, const Params &p, const Fields &f, hip
   return hipGetLastError();
 }
 
+// GMREDI_RESIDUAL_FLOW into uRes / vRes / wRes: after the step's tensor (it reads Psi at i+1, j+1)
+// and the velocities' halo exchange, before the first multi-dimensional pass
+hipError_t launch_gm_residual_flow(const Dims &d, const Params &p, const Fields &f, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_residual_flow, dim3(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr)), dim3(MG_PLANE_THREADS), 0, s, d, p,
+                     f);
+  return hipGetLastError();
+}
+
 hipError_t launch_phys_ring(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s);
 // the 16-byte form (k_oceanic_phys2) or the per-point one
 static bool phys_v2(const Dims &d, const Params &p, const Fields &f) {
@@ -1334,12 +1372,17 @@ static bool tracer_march_on(const Dims &d) {
 
 // impl = false: the right-hand side only (the implicit solve is launched by the caller)
 // nLaunch (or null): the kernel launches issued are added to it, counted where they are issued
-hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a, const int *iterPtr,
-                              hipStream_t s, bool impl, int *nLaunch) {
+// resFlow: GM_AdvForm's residual flow is in uRes / vRes / wRes (launch_gm_residual_flow) and the
+// multi-dimensional passes advect by it; the right-hand side keeps f (a multi-dimensional tracer
+// takes only the Redi diffusion there, a scheme-2 tracer forms the bolus terms on the fly)
+hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f0, const TracerArgs &a, const int *iterPtr,
+                              hipStream_t s, bool impl, int *nLaunch, bool resFlow) {
   struct Count { int n, *out; ~Count() { if (out) *out += n; } } cnt{0, nLaunch};
 #define MG_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); cnt.n++; } while (0)
   const dim3 blk(MG_PLANE_THREADS), grd(mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr));
+  const Fields &f = f0;
   if (a.multiDim) {
+    const Fields f = resFlow ? res_flow_fields(f0) : f0;   // (the passes only)
     const dim3 fgrd(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr));
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: fused per-point X and Y passes

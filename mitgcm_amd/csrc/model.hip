@@ -87,7 +87,7 @@ bool phys_ring_ok(const Dims &, const Params &, const Fields &);
 hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
                                bool ring = false);
 hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, const TracerArgs &, const int *, hipStream_t,
-                              bool impl = true, int *nLaunch = nullptr);
+                              bool impl = true, int *nLaunch = nullptr, bool resFlow = false);
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
 hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
                              hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true);
@@ -97,6 +97,7 @@ hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, c
                                  int *, hipStream_t, int fromX, int empNext);
 bool dyn_thermo_takes_gm(const Params &);
 hipError_t launch_gm_tensor(const Dims &, const Params &, const Fields &, hipStream_t);
+hipError_t launch_gm_residual_flow(const Dims &, const Params &, const Fields &, hipStream_t);
 bool gm_phi_fusable(const Dims &, const Params &);
 hipError_t launch_gm_phi(const Dims &, const Params &, const Fields &, hipStream_t, bool op = false);
 bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
@@ -105,7 +106,7 @@ hipError_t launch_tracer_hpair(const Dims &, const Params &, const Fields &, con
 hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, hipStream_t);
 bool ptr_batch_ok(const Dims &, const Params &, bool md);
 hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int, int, int,
-                                 int, const int *, hipStream_t, int *nLaunch = nullptr);
+                                 int, const int *, hipStream_t, int *nLaunch = nullptr, bool resFlow = false);
 }  // namespace mgcm
 
 using namespace mgcm;
@@ -284,6 +285,8 @@ struct mgcm_model {
   // the last ptracers_on (mgcm_get_param "ptrRoute", "ptrLaunches"): 0 no tracers, 1 functional, 2 batched;
   // the kernel launches it issued for PTRACERS_INTEGRATE, the exchanges not counted
   int ptrRoute = 0, ptrLaunches = 0;
+  // whether the last THERMODYNAMICS launched k_gm_residual_flow (mgcm_get_param "gmResFlow"; StepPlan::resFlow)
+  int gmResFlow = 0;
   // pkg/ptracers (mgcm_ptracers_alloc): a third arena, sized at run time, of PTR_NF 3-D fields
   // per tracer -- the ping-pong pair, gpTrNm1 and the tracer's own T*, advScr1 (also the
   // marches' c'), advScr2 and gAdv scratch: the batched kernels run the tracers concurrently
@@ -1178,6 +1181,8 @@ double mgcm_get_param(mgcm_model *m, const char *name) {
   // the route of the last ptracers_on (0 no tracers, 1 functional, 2 batched) and its launches
   if (!strcmp(name, "ptrRoute")) return (double)m->ptrRoute;
   if (!strcmp(name, "ptrLaunches")) return (double)m->ptrLaunches;
+  // 1 when the last THERMODYNAMICS formed GM_AdvForm's residual flow for its multi-dimensional tracers
+  if (!strcmp(name, "gmResFlow")) return (double)m->gmResFlow;
   // whether the selected kernel solves with fused multiply-adds (k_cg2d_bxy honours cg2dUseFMA)
   if (!strcmp(name, "cg2dFMA")) return (m->solver == Cg2dSolver::Bxy && m->p.cg2dUseFMA) ? 1.0 : 0.0;
   for (auto &pd : PARAMS)
@@ -1587,9 +1592,6 @@ int mgcm_init(mgcm_model *m) {
     return set_err("mgcm_init: tempAdvScheme %d not implemented on the device", m->p.tempAdvScheme);
   if (m->p.saltStepping && !okScheme(m->p.saltAdvScheme, "saltVertAdvScheme"))
     return set_err("mgcm_init: saltAdvScheme %d not implemented on the device", m->p.saltAdvScheme);
-  if (m->p.useGMRedi && m->p.GM_AdvForm && m->p.multiDimAdvection &&
-      ((m->p.tempStepping && mdScheme(m->p.tempAdvScheme)) || (m->p.saltStepping && mdScheme(m->p.saltAdvScheme))))
-    return set_err("mgcm_init: GM_AdvForm with multi-dimensional advection is not implemented on the device");
   if (m->p.useGMRedi && m->p.GM_AdvForm && m->p.GM_skewflx != 0.0)
     return set_err("mgcm_init: GM_AdvForm needs GM_skewflx = 0 (gmredi_readparms.F:243-244)");
   // pkg/ptracers: a tracer is accepted with exactly the options salt would be accepted with
@@ -1611,9 +1613,6 @@ int mgcm_init(mgcm_model *m) {
     }
     if (!okScheme(s, "PTRACERS_vertAdvScheme"))
       return set_err("mgcm_init: pTracer%02d: advScheme %d not implemented on the device", no, s);
-    const bool gm = m->p.useGMRedi && t.useGMRedi != 0;
-    if (gm && m->p.GM_AdvForm && m->p.multiDimAdvection && mdScheme(s))
-      return set_err("mgcm_init: pTracer%02d: GM_AdvForm with multi-dimensional advection is not implemented on the device", no);
   }
   if (m->p.eosType != 0 && m->p.eosType != 1) return set_err("mgcm_init: eosType %d not implemented", m->p.eosType);
   if (m->d.Nr > 64) return set_err("mgcm_init: Nr = %d > 64 (column kernels hold a column in one workgroup)", m->d.Nr);
@@ -1842,6 +1841,7 @@ static int ptr_tables_sync(mgcm_model *m) {
 // swap together (CYCLE_TRACER)
 static int ptracers_on(mgcm_model *m, hipStream_t st) {
   const int n = (int)m->ptr.size();
+  const bool resFlow = m->gmResFlow != 0;   // (res_flow_on ran ahead: every multi-dimensional tracer takes it)
   m->ptrRoute = 0;
   m->ptrLaunches = 0;
   if (!n) return 0;
@@ -1849,14 +1849,14 @@ static int ptracers_on(mgcm_model *m, hipStream_t st) {
   if (ptr_batched(m)) {
     m->ptrRoute = 2;
     TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
-                                        m->ptrNGM, m->d_ctr, st, &m->ptrLaunches));
+                                        m->ptrNGM, m->d_ctr, st, &m->ptrLaunches, resFlow));
   } else {
     m->ptrRoute = 1;
     for (int i = 0; i < n; i++) {
       const TracerArgs a = tracer_args_ptr(m, i, m->ptrFlip);
       Params pp = m->p;
       pp.useGMRedi = a.gm;
-      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st, true, &m->ptrLaunches));
+      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st, true, &m->ptrLaunches, resFlow));
     }
   }
   for (int i0 = 0; i0 < n; i0 += MG_XMAX) {
@@ -1868,8 +1868,14 @@ static int ptracers_on(mgcm_model *m, hipStream_t st) {
   return 0;
 }
 
+// GMREDI_RESIDUAL_FLOW (thermodynamics.F:252-270) at the head of THERMODYNAMICS, where the plan
+// has it (StepPlan::resFlow); defined with the plan
+static int res_flow_on(mgcm_model *m, hipStream_t st);
+
 // TEMP_INTEGRATE / SALT_INTEGRATE (and PTRACERS_INTEGRATE) on stream `st` (the ping-pong swaps are host-side)
 static int tracers_on(mgcm_model *m, hipStream_t st) {
+  if (res_flow_on(m, st)) return -1;
+  const bool resFlow = m->gmResFlow != 0;
   const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
   if (tracer_hpair_ok(m->d, m->p, aT, aS)) {   // small grids: both tracers per launch
     TIMED(K_TEMP, launch_tracer_hpair(m->d, m->p, m->f, aT, aS, m->d_ctr, st));
@@ -1878,11 +1884,11 @@ static int tracers_on(mgcm_model *m, hipStream_t st) {
     return ptracers_on(m, st);
   }
   if (m->p.tempStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, tracer_args(m, false), m->d_ctr, st));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aT, m->d_ctr, st, true, nullptr, resFlow));
     std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new theta is the other buffer
   }
   if (m->p.saltStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, tracer_args(m, true), m->d_ctr, st));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aS, m->d_ctr, st, true, nullptr, resFlow));
     std::swap(m->f.salt, m->f.saltNext);
   }
   return ptracers_on(m, st);
@@ -2181,8 +2187,20 @@ struct StepPlan {
   // step's own CALC_PHI_HYD + del2uv are already done; phiNext: it runs the next step's;
   // empNext: the next step's DO_OCEANIC_PHYS left its EmPmR in EmPmRnext (rstar.h)
   bool pipeOk, phiPipeOk, pipe, hoist, valid, phiPipe, phiNext, empNext;
+  // GMREDI_RESIDUAL_FLOW as a launch of its own (k_gm_residual_flow -> uRes, vRes, wRes): under
+  // GM_AdvForm when a stepped tracer -- theta, salt or a passive one -- takes GAD_ADVECTION's
+  // multi-dimensional passes, which then advect by those fields.  It reads the step's whole
+  // tensor (Psi at i+1, j+1) and u, v, w with the halos THERMODYNAMICS sees, so it opens
+  // THERMODYNAMICS wherever that runs (tracers_on, on the tracers' stream: after the tensor's
+  // grid, and on the staggered cube after DO_STAGGER_FIELDS_EXCHANGES); resFlowFold: where the
+  // fold steps theta and salt (scheme 2) in DYNAMICS' grids, it opens PTRACERS_INTEGRATE instead.
+  // Such a step keeps the plain plan (pipeOk): the pipelined step's hoisted tensor is checked
+  // against the scheme-2 right-hand side, which reads Psi one point outside the interior at
+  // most, and the residual flow reads it over the whole slab
+  bool resFlow, resFlowFold;
 };
 static TracerArgs tracer_args(const mgcm_model *m, bool salt);
+static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip);
 static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const Params &p = m->p;
   const Dims &d = m->d;
@@ -2201,6 +2219,11 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const bool ringSep = mom_ring_separable(d, p);
   pl.ringLate = pl.forkLate && ringSep && mg_fuse_on(MG_FUSE_RING);
   pl.ringAside = pl.thermoLate && pl.ringLate;
+  pl.resFlow = false;
+  if (p.useGMRedi && p.GM_AdvForm && pl.tracers) {
+    pl.resFlow = (p.tempStepping && tracer_args(m, false).multiDim) || (p.saltStepping && tracer_args(m, true).multiDim);
+    for (int i = 0; i < (int)m->ptr.size() && !pl.resFlow; i++) pl.resFlow = tracer_args_ptr(m, i, 0).multiDim != 0;
+  }
   pl.dtFused = pl.forkable && pl.rstar && dyn_thermo_fusable(d, p, tracer_args(m, false), tracer_args(m, true));
   // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
   const bool gmFold = pl.dtFused && dyn_thermo_takes_gm(p);
@@ -2218,8 +2241,9 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
               mg_hfuse(MG_FUSE_ENDS, d.nx, d.ny, d.nT, d.Nr);
   // (JMD95P reads totPhiHyd's halo: exact at the exchange source only where it is exchanged)
   const bool totPhiHalo = p.eosType == 1 && p.selectP_inEOS_Zc == 2 && !p.storePhiHyd4Phys;
+  pl.resFlowFold = pl.resFlow && pl.dtFused;
   pl.pipeOk = gmFold && pl.sfpFused && pl.endFused && mg_fuse_on(MG_FUSE_PIPE) && p.select_rStar > 0 &&
-              p.useRealFreshWaterFlux && p.exactConserv && m->d_srcOf && !totPhiHalo;
+              p.useRealFreshWaterFlux && p.exactConserv && m->d_srcOf && !totPhiHalo && !pl.resFlow;
   pl.phiPipeOk = pl.pipeOk && phi_pipe_ok(d, p);
   pl.pipe = mode != STEP_PLAIN;
   pl.hoist = mode == STEP_HOIST;
@@ -2239,6 +2263,12 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
 static int step_layout_bits(const StepPlan &pl) {
   return (pl.dtFused ? 1 : 0) | (pl.forkable && !pl.dtFused ? 4 : 0) | (pl.forkable && pl.forkLate ? 8 : 0) |
          (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0);
+}
+
+static int res_flow_on(mgcm_model *m, hipStream_t st) {
+  m->gmResFlow = plan_step(m, STEP_PLAIN).resFlow ? 1 : 0;
+  if (m->gmResFlow) TIMED(K_TEMP, launch_gm_residual_flow(m->d, m->p, m->f, st));
+  return 0;
 }
 
 // THERMODYNAMICS onto the second stream (after the model stream's work so far), evJoin behind
@@ -2265,6 +2295,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   // the multi-workgroup CG2D keeps its CUs to itself while the tracers run beside it
   m->mwg.exclusive = pl.thermoLate ? 1 : 0;
   m->stepLayout = step_layout_bits(pl);
+  m->gmResFlow = 0;
   if (!pl.pipe) TIMED(K_PHYS, launch_oceanic_phys(m->d, m->p, m->f, m->d_ctr, m->stream, pl.physGm, pl.ringPhys));
   if (pl.forkEarly && fork_thermo(m, false, false)) return -1;
   if (pl.thermoInline && tracers_on(m, m->stream)) return -1;
@@ -2276,6 +2307,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
       std::swap(m->f.salt, m->f.saltNext);
       // PTRACERS_INTEGRATE where the fold replaced tracers_on: right behind it, before
       // UPDATE_R_STAR rewrites the hFac it reads
+      if (pl.resFlowFold && res_flow_on(m, m->stream)) return -1;
       if (ptracers_on(m, m->stream)) return -1;
     } else if (pl.gmPhi) {
       TIMED(K_PHI, launch_gm_phi(m->d, m->p, m->f, m->stream));

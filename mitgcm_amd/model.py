@@ -303,6 +303,14 @@ class Model:
         r = int(lib().mgcm_get_param(self.h, b"ptrRoute"))
         return {"route": ("none", "functional", "batched")[r], "launches": int(lib().mgcm_get_param(self.h, b"ptrLaunches"))}
 
+    def gm_res_flow(self):
+        """True when the last THERMODYNAMICS issued formed GM_AdvForm's residual flow as fields
+        (mgcm_get_param 'gmResFlow': k_gm_residual_flow ran, and the multi-dimensional advection of
+        theta, salt and the passive tracers took uRes, vRes, wRes): useGMRedi with GM_AdvForm and
+        at least one stepped tracer on scheme 30 or 33.  A replayed step graph keeps what it was
+        captured with."""
+        return lib().mgcm_get_param(self.h, b"gmResFlow") != 0.0
+
     def cg2d_fma(self):
         """True when the selected CG2D kernel solves in fused multiply-adds (cg2dUseFMA): the
         device-order oracle must then evaluate the same fma chains (Oracle.set_sum_plan(fma=))."""

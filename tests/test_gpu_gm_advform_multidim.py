@@ -1,0 +1,402 @@
+"""GM_AdvForm with multi-dimensional advection (schemes 30 / 33): GMREDI_RESIDUAL_FLOW as a
+launch of its own (kernels_thermo.hip k_gm_residual_flow -> uRes, vRes, wRes), read by every
+multi-dimensional pass of theta, salt and the passive tracers in place of the Eulerian velocity
+(thermodynamics.F:252-270; the oracle forms the same fields in oracle/thermo.c:384-409).
+
+  1  one THERMODYNAMICS call on global_ocean.90x40x15 (one tile, OL = 3) with schemes 30 and 33,
+     and once with multiDimCompressible (the general form of GAD_ADVECTION on a lat-lon map);
+  2  4 steps of the same configuration, scheme 30, on 1 x 1 and 2 x 2 tiles;
+  3  4 steps of global_ocean.cs32x15 with scheme 33 and the experiment's own GM options
+     (GM_AdvForm = T) on tiles of 32 x 32, 16 x 16 (corner tiles only) and 8 x 8 (interior
+     tiles), and once with scheme 30;
+  4  the feature is seen: the advective and the skew form give different theta, Psi is not zero,
+     gmResFlow reads 1; with scheme 2 it reads 0 and the step issues what it issues in skew form;
+  5  passive tracers on schemes 33, 30 and 2 on both routes (MGCM_PTR_BATCH = 0 / 1) against the
+     oracle's salt stand-in (test_gpu_ptracers.py), on cs32x15 and tutorial_global_oce_latlon;
+  6  forward_step(6) against six forward_step(1), and with the pipelined-step bits off;
+  7  two tile-sharded processes against one.
+
+Every comparison with the oracle is np.array_equal on tile interiors.  Before this feature
+every make_model below ended in MgcmError ("GM_AdvForm with multi-dimensional advection is not
+implemented on the device").  The premise -- the oracle runs these configurations, and tells the
+two forms of GM apart -- is guarded on the CPU by test_oracle_gm_advform_multidim.py."""
+import functools
+import os
+import socket
+
+import numpy as np
+import pytest
+
+import shapes
+from test_gpu_cs32x15 import STATE as CS32_STATE
+from test_gpu_ocean90 import STATE as OCEAN90_STATE
+from test_gpu_ptracers import LATLON_STATE, _inner, _wet_random
+
+pytestmark = pytest.mark.gpu
+
+GM_ADV = {"GM_AdvForm": 1, "GM_skewflx": 0.0}
+GM_SKEW = {"GM_AdvForm": 0, "GM_skewflx": 1.0}
+STEP_FIELDS = ("uVel", "vVel", "wVel", "theta", "salt", "etaN", "etaH", "gtNm1", "gsNm1")
+# MGCM_STEP_FUSE as common.h's default composes it
+STEP_FUSE_DEFAULT = 1 | 4 | 8 | 128 | 256 | 1024 | 2048 | 4096 | 8192 | 16384 | 32768
+
+
+def adv(scheme, **over):
+    return dict({"tempAdvScheme": scheme, "tempVertAdvScheme": scheme, "saltAdvScheme": scheme,
+                 "saltVertAdvScheme": scheme, "multiDimAdvection": 1}, **over)
+
+
+def _param(m, name):
+    from mitgcm_amd._lib import lib
+    return lib().mgcm_get_param(m.h, name.encode())
+
+
+def _put_state(m, state, myIter):
+    from mitgcm_amd._lib import lib
+    for n, v in state.items():
+        m.put(n, v)
+    lib().mgcm_set_param(m.h, b"myIter", float(myIter))
+
+
+def _ocean90_cfg(over, nSx=1, nSy=1):
+    from mitgcm_amd import configs
+    return lambda: configs.global_ocean_90x40x15(nSx=nSx, nSy=nSy, params_over=over)
+
+
+def _cs32_cfg(over, tile=(32, 32)):
+    from mitgcm_amd import configs
+    return lambda: configs.global_ocean_cs32x15(sNx=tile[0], sNy=tile[1], params_over=over)
+
+
+# ---- 1: one THERMODYNAMICS call, lat-lon ---------------------------------------------------------
+@pytest.mark.parametrize("scheme,comp", [(30, 0), (33, 0), (33, 1)], ids=["dst3", "dst3fl", "dst3fl_compressible"])
+def test_ocean90_one_thermodynamics_bitexact(scheme, comp):
+    """Two oracle steps; their state goes to the device, which runs DO_OCEANIC_PHYS (the tensor
+    and Psi) and THERMODYNAMICS itself, as test_ocean90_oceanic_phys_and_thermodynamics_bitexact
+    does; the oracle runs EXTERNAL_FIELDS_LOAD, DO_OCEANIC_PHYS and THERMODYNAMICS."""
+    from mitgcm_amd import configs
+    from oracle.harness import ocean90_oracle
+    over = adv(scheme, multiDimCompressible=comp, **GM_ADV)
+    o, g = ocean90_oracle(params_over=over)
+    for _ in range(2):
+        o.forward_step()
+    m = configs.make_model(_ocean90_cfg(over))
+    try:
+        assert (g.nTiles, g.OLx) == (1, 3)
+        _put_state(m, {n: np.array(o.arr(n)) for n in OCEAN90_STATE}, o.get("myIter"))
+        m.thermodynamics()
+        o.L.oracle_fields_load(o.h)
+        o.L.oracle_oceanic_phys(o.h)
+        o.L.oracle_thermodynamics(o.h)
+        assert m.gm_res_flow()
+        assert np.abs(m.get("GM_PsiX")).max() > 0.0
+        inner = _inner(g)
+        bad = []
+        for n in ("theta", "salt"):
+            dev = m.get(n)
+            ref = np.array(o.arr(n)).reshape(dev.shape)
+            print(n, "max |device - oracle| on the interior:", float(np.abs(dev - ref)[inner].max()))
+            if not np.array_equal(dev[inner], ref[inner]):
+                bad.append((n, float(np.abs(dev - ref)[inner].max())))
+        assert not bad, bad
+    finally:
+        m.close()
+
+
+# ---- 2: multi-step, lat-lon ----------------------------------------------------------------------
+@pytest.mark.parametrize("tiling", [(1, 1), (2, 2)], ids=["1x1", "2x2"])
+def test_ocean90_4_steps_bitexact(tiling):
+    from oracle.harness import ocean90_oracle
+    nSx, nSy = tiling
+    over = adv(30, **GM_ADV)
+    kernel, parts, layout = shapes.assert_bitexact_steps(
+        _ocean90_cfg(over, nSx, nSy), 4, STEP_FIELDS,
+        oracle_factory=lambda cfg: ocean90_oracle(nSx=nSx, nSy=nSy, params_over=over),
+        after=lambda m: _assert_res_flow(m, True))
+    print("ocean90 on %d x %d tiles, scheme 30, GM_AdvForm: CG2D %s, %d part(s), step layout %s" % (
+        nSx, nSy, kernel, parts, sorted(k for k, v in layout.items() if v)))
+
+
+def _assert_res_flow(m, want):
+    assert m.gm_res_flow() == want
+
+
+# ---- 3: multi-step, cube -------------------------------------------------------------------------
+CS32_RUNS = [((32, 32), 33), ((16, 16), 33), ((8, 8), 33), ((32, 32), 30)]
+
+
+@pytest.mark.parametrize("tile,scheme", CS32_RUNS, ids=["%dx%d-%d" % (t[0], t[1], s) for t, s in CS32_RUNS])
+def test_cs32x15_4_steps_bitexact(tile, scheme):
+    """CS32_TRACERS["dst3fl"] of test_gpu_shapes_cube.py without its skew-form override."""
+    from oracle.harness import cs32x15_oracle
+    sNx, sNy = tile
+    over = adv(scheme, storePhiHyd4Phys=1)
+    kernel, parts, layout = shapes.assert_bitexact_steps(
+        _cs32_cfg(over, tile), 4, CS32_STATE,
+        oracle_factory=lambda cfg: cs32x15_oracle(sNx=sNx, sNy=sNy, params_over=over),
+        after=lambda m: _assert_res_flow(m, True))
+    print("cs32x15 on %d tiles of %d x %d, scheme %d, GM_AdvForm: CG2D %s, step layout %s" % (
+        parts, sNx, sNy, scheme, kernel, sorted(k for k, v in layout.items() if v)))
+
+
+# ---- 4: not vacuous ------------------------------------------------------------------------------
+TIMED = ("mom_step", "sfp_rhs", "cg2d", "exchange", "eta_update", "correction", "continuity", "oceanic_phys",
+         "temp_step", "r_star", "phi_hyd")
+
+
+def _three_steps(over):
+    """theta after 3 steps, max |GM_PsiX|, gmResFlow, and what one more, timed, step issues per
+    routine (Model.kernel_ms's counts)."""
+    from mitgcm_amd import configs
+    m = configs.make_model(_cs32_cfg(over))
+    try:
+        m.forward_step(3)
+        m.sync()
+        theta, psi, res = m.get("theta"), float(np.abs(m.get("GM_PsiX")).max()), m.gm_res_flow()
+        m.kernel_timing(True)
+        m.forward_step(1)
+        m.sync()
+        counts = {k: m.kernel_ms(k)[1] for k in TIMED}
+        m.kernel_timing(False)
+        assert m.gm_res_flow() == res
+    finally:
+        m.close()
+    return theta, psi, res, counts
+
+
+def test_cs32x15_the_two_forms_differ_and_scheme_2_is_left_alone():
+    th_adv, psi, res, n_adv = _three_steps(adv(33))
+    th_skew, psi_skew, res_skew, n_skew = _three_steps(adv(33, **GM_SKEW))
+    assert res and not res_skew
+    assert psi > 0.0 and psi_skew == 0.0
+    assert np.isfinite(th_adv).all() and not np.array_equal(th_adv, th_skew)
+    # the residual flow is the one launch more, in THERMODYNAMICS
+    assert n_adv == dict(n_skew, temp_step=n_skew["temp_step"] + 1), (n_adv, n_skew)
+    # scheme 2 (the experiment itself): no residual-flow launch, the same launches as in skew form
+    _, psi2, res2, n2 = _three_steps({})
+    _, _, res2s, n2s = _three_steps(dict(GM_SKEW))
+    assert psi2 > 0.0 and not res2 and not res2s
+    assert n2 == n2s, (n2, n2s)
+
+
+# ---- 5: passive tracers, both routes -------------------------------------------------------------
+PTR_SPECS = (dict(advScheme=33, diffKr=3e-5, useGMRedi=1), dict(advScheme=30, diffKr=1e-5, useGMRedi=1),
+             dict(advScheme=2, diffKh=300.0, useGMRedi=1))
+
+
+def _latlon_cfg(**kw):
+    from mitgcm_amd import configs
+    out = configs.global_oce_latlon(**kw)
+    return (out[0], dict(out[1], multiDimAdvection=1, **GM_ADV)) + tuple(out[2:])
+
+
+def _cs32_ptr_cfg():
+    return _cs32_cfg({"multiDimAdvection": 1})()
+
+
+@functools.lru_cache(maxsize=None)
+def _standin_reference(which):
+    """test_gpu_ptracers.py's _latlon_reference under GM_AdvForm, for either experiment: oracle
+    steps, DO_OCEANIC_PHYS with the true salt, then per tracer THERMODYNAMICS with salt := X,
+    saltForcing = 0 and the tracer's scheme and diffusivities.  Computed once and shared by the
+    two routes (do not modify)."""
+    from oracle.harness import cs32x15_oracle, latlon_oracle
+    if which == "latlon":
+        o, g = latlon_oracle()
+        o.set(**GM_ADV)
+        names, nsteps = LATLON_STATE, 3
+    else:
+        o, g = cs32x15_oracle()
+        names, nsteps = CS32_STATE, 2
+    assert o.get("useGMRedi") == 1 and o.get("GM_AdvForm") == 1 and o.get("GM_skewflx") == 0.0
+    for _ in range(nsteps):
+        o.forward_step()
+    state = {n: np.array(o.arr(n)) for n in names}
+    myIter = o.get("myIter")
+    o.L.oracle_fields_load(o.h)
+    o.L.oracle_oceanic_phys(o.h)
+    assert np.abs(np.array(o.arr("GM_PsiX"))).max() > 0.0
+    keep = {n: np.array(o.arr(n)) for n in ("theta", "salt", "gtNm1", "gsNm1", "surfaceForcingS")}
+    rng = np.random.default_rng(20261021)
+    xs = [_wet_random(g, rng) for _ in PTR_SPECS]
+    out = []
+    for sp, x in zip(PTR_SPECS, xs):
+        for n, v in keep.items():
+            o.arr(n)[:] = v
+        o.arr("salt")[:] = x
+        s = sp["advScheme"]
+        o.set(saltAdvScheme=s, saltVertAdvScheme=s, diffKhS=sp.get("diffKh", 0.0), diffKrS=sp.get("diffKr", 0.0),
+              saltForcing=0, multiDimAdvection=1)
+        o.L.oracle_thermodynamics(o.h)
+        out.append((np.array(o.arr("salt")), np.array(o.arr("gsNm1"))))
+    for a in list(state.values()) + xs + [b for pair in out for b in pair]:
+        a.setflags(write=False)
+    return g, state, myIter, keep["gsNm1"], xs, out
+
+
+@pytest.mark.parametrize("batch", [0, 1])
+@pytest.mark.parametrize("which", ["cs32x15", "latlon"])
+def test_ptracers_one_thermodynamics_bitexact(which, batch, monkeypatch):
+    from mitgcm_amd import configs
+    monkeypatch.setenv("MGCM_PTR_BATCH", str(batch))
+    g, state, myIter, gs0, xs, ref = _standin_reference(which)
+    cfg = _latlon_cfg if which == "latlon" else _cs32_ptr_cfg
+    m = configs.make_model(cfg, ptracers=[dict(sp, init=x) for sp, x in zip(PTR_SPECS, xs)])
+    plain = configs.make_model(cfg)
+    try:
+        for x in (m, plain):
+            _put_state(x, state, myIter)
+        m.put("gpTrNm1_03", gs0)
+        m.thermodynamics()
+        plain.thermodynamics()
+        assert m.gm_res_flow() and not plain.gm_res_flow()   # (theta and salt are on scheme 2)
+        assert m.ptracers_route()["route"] == ("batched" if batch else "functional"), m.ptracers_route()
+        inner = _inner(g)
+        bad = []
+        for no, (salt, gs) in enumerate(ref, 1):
+            dev = m.get("pTracer%02d" % no)
+            print("pTracer%02d max |device - oracle| on the interior:" % no, float(np.abs(dev - salt)[inner].max()))
+            if not np.array_equal(dev[inner], salt[inner]):
+                bad.append((no, float(np.abs(dev - salt)[inner].max())))
+            assert not np.array_equal(dev[inner], xs[no - 1][inner])
+        if not np.array_equal(m.get("gpTrNm1_03")[inner], ref[2][1][inner]):
+            bad.append("gpTrNm1_03")
+        assert not bad, bad
+        for n in ("theta", "salt", "gtNm1", "gsNm1"):
+            assert np.array_equal(m.get(n), plain.get(n)), n
+    finally:
+        m.close()
+        plain.close()
+
+
+# ---- 6: graphs and the pipelined step ------------------------------------------------------------
+def test_ocean90_graph_replay_and_pipe_bits(monkeypatch):
+    """forward_step(6) (the replayed two-step graphs) against six forward_step(1) (the one-step
+    graphs of both parities) and against forward_step(6) with MG_FUSE_PIPE and MG_FUSE_PHIP off."""
+    from mitgcm_amd import configs
+    monkeypatch.setenv("MGCM_OVERLAP", "1")   # (no timing-dependent choice of the layout)
+    cfg = _ocean90_cfg(adv(33, **GM_ADV))
+    res = {}
+    for how in ("call", "single", "nopipe"):
+        if how == "nopipe":
+            monkeypatch.setenv("MGCM_STEP_FUSE", str(STEP_FUSE_DEFAULT & ~(16384 | 32768)))
+        m = configs.make_model(cfg)
+        try:
+            if how == "single":
+                for _ in range(6):
+                    m.forward_step(1)
+            else:
+                m.forward_step(6)
+            m.sync()
+            assert m.gm_res_flow()
+            res[how] = {n: m.get(n) for n in STEP_FIELDS}
+            res[how]["stats"] = m.solve_stats()   # (the last step's solve)
+        finally:
+            m.close()
+    for how in ("single", "nopipe"):
+        for n in STEP_FIELDS:
+            assert np.array_equal(res["call"][n], res[how][n]), (how, n, np.abs(res["call"][n] - res[how][n]).max())
+        assert res["call"]["stats"] == res[how]["stats"], how
+    assert np.isfinite(res["call"]["theta"]).all()
+
+
+@pytest.mark.parametrize("batch", [0, 1])
+def test_ocean90_fold_with_multidim_ptracer(batch, monkeypatch):
+    """theta and salt on scheme 2 keep the fold (THERMODYNAMICS in DYNAMICS' grids); a scheme-33
+    passive tracer then needs the residual flow ahead of PTRACERS_INTEGRATE (StepPlan::resFlowFold),
+    and the step is not pipelined.  Against the same model without the fold (MG_FUSE_DT off), whose
+    residual flow opens tracers_on -- the route tests 1 to 5 pin to the oracle -- bit for bit."""
+    from mitgcm_amd import configs
+    monkeypatch.setenv("MGCM_PTR_BATCH", str(batch))
+    monkeypatch.setenv("MGCM_OVERLAP", "1")
+    cfg = _ocean90_cfg(dict(GM_ADV, multiDimAdvection=1))
+    g = cfg()[0]
+    x = _wet_random(g, np.random.default_rng(9040))
+    names = STEP_FIELDS + ("pTracer01",)
+    res = {}
+    for fold in (True, False):
+        if not fold:
+            monkeypatch.setenv("MGCM_STEP_FUSE", str(STEP_FUSE_DEFAULT & ~128))
+        m = configs.make_model(cfg, ptracers=[dict(advScheme=33, diffKr=3e-5, init=x)])
+        try:
+            m.forward_step(6)
+            m.sync()
+            lay = m.step_layout()
+            assert lay["dyn_thermo_fused"] == fold and not lay["pipelined"], lay
+            assert m.gm_res_flow()
+            res[fold] = {n: m.get(n) for n in names}
+        finally:
+            m.close()
+    for n in names:
+        assert np.array_equal(res[True][n], res[False][n]), (n, np.abs(res[True][n] - res[False][n]).max())
+    assert not np.array_equal(res[True]["pTracer01"][_inner(g)], x[_inner(g)])
+
+
+# ---- 7: tile-sharded -----------------------------------------------------------------------------
+SHARD_FIELDS = ("uVel", "vVel", "wVel", "theta", "salt", "etaN", "etaH")
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def _shard_worker(rank, world, port, nsteps, q):
+    import torch
+    import torch.distributed as dist
+    from mitgcm_amd import configs
+    from mitgcm_amd.parallel import ShardedModel
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        torch.cuda.set_device(0)
+        cfg = _cs32_cfg(adv(33))
+        m = configs.make_model(cfg)
+        sm = ShardedModel(m, dist, device=torch.device("cuda", 0), cg2d="replicated", overlap="thermo")
+        sm.forward_step(nsteps)
+        m.sync()
+        full = {n: sm.gather_field(n) for n in SHARD_FIELDS}
+        res = {"t0": sm.t0, "nT": sm.nT, "res_flow": m.gm_res_flow()}
+        if rank == 0:
+            ref = configs.make_model(cfg)
+            ref.forward_step(nsteps)
+            ref.sync()
+            res["diff"] = {n: float(np.max(np.abs(full[n] - ref.get(n)))) for n in SHARD_FIELDS}
+            res["equal"] = {n: bool(np.array_equal(full[n], ref.get(n))) for n in SHARD_FIELDS}
+            res["finite"] = bool(np.isfinite(ref.get("theta")).all())
+            ref.close()
+        m.close()
+        q.put((rank, res))
+    except Exception:
+        import traceback
+        q.put((rank, {"error": traceback.format_exc()}))
+        raise
+    finally:
+        dist.destroy_process_group()
+
+
+def test_cs32x15_two_sharded_processes_bit_identical():
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    world, nsteps = 2, 3
+    procs = [ctx.Process(target=_shard_worker, args=(r, world, port, nsteps, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    out = {}
+    for _ in procs:
+        rank, res = q.get(timeout=300)
+        assert "error" not in res, "rank %d: %s" % (rank, res["error"])
+        out[rank] = res
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    r0 = out[0]
+    print("cs32x15, scheme 33, GM_AdvForm, sharded x2: max |diff| vs 1 process:", r0["diff"])
+    assert all(r["res_flow"] for r in out.values())
+    assert r0["finite"] and all(r0["equal"].values()), r0["diff"]
+    assert sorted((r["t0"], r["nT"]) for r in out.values()) == [(0, 3), (3, 3)]

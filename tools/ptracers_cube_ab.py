@@ -2,7 +2,8 @@
 """A/B of the two passive-tracer routes on the cube sphere ("Passive
 tracers"): global_ocean_cs32x15 (BASELINE config 3: staggered, r*, the tracers on the critical
 path before UPDATE_R_STAR) with N = 0, 1, 4, 8 copies of a scheme-33 tracer started as salt,
-useGMRedi = 0 (GM_AdvForm refuses multi-dimensional GM tracers), diffKr = 3e-5.  Per N one
+useGMRedi = 0 (chosen when GM_AdvForm refused multi-dimensional GM tracers; since the residual
+flow became a launch of its own, k_gm_residual_flow, every N >= 1 includes it), diffKr = 3e-5.  Per N one
 model per route (MGCM_PTR_BATCH is read when a step graph is captured, and a model keeps the
 route of its graphs); forward_step(100) after 20 warm-up steps, host clock around a
 synchronise; the two routes timed alternately, batched first, three alternations in one process.
