@@ -370,29 +370,21 @@ struct TracerArgs {
   int limiter;          // multi-dim face fluxes: 1 DST3FL (scheme 33), 0 DST3 (scheme 30)
   int scheme;           // the advection scheme (2 C2, 3 U3, 4 C4 inside GAD_CALC_RHS; 30/33 multi-dim)
   double *gNm2;         // ADAMS_BASHFORTH3: gtNm(:,:,:,2) (gNm1 is slot 1)
-  // passive tracers (pkg/ptracers; all "off" for theta and salt, whose arithmetic they leave alone)
+  // passive tracers' forcing (pkg/ptracers; "off" for theta and salt, whose arithmetic it leaves alone)
   double relaxRate;     // 1/surfRelaxTau, 0: no surface relaxation (ptracers_forcing_surf.F)
   double relaxVal;      // the value the surface level is relaxed to
   double src;           // interior source at every k != 1 (ptracers_apply_forcing.F), 0: none
-  int gm;               // the tracer's useGMRedi (PTRACERS_useGMRedi): both passive-tracer routes step the
-                        // tracer with Params.useGMRedi set to it (ptracers_on, k_ptr_rhs, k_ptr_impl)
-  // the tracer's own multi-dimensional advection scratch (null: the model's advScr1 / advScr2 / gAdv)
+  // set for every tracer (model.hip tracer_args, tracer_args_ptr)
+  int gm;               // the tracer takes GM/Redi: Params.useGMRedi, and for a passive tracer its own
+                        // PTRACERS_useGMRedi as well (k_tracer_rhs<GM>, the implicit solve's Kwz terms)
+  // the multi-dimensional passes' loc, vol and advective tendency: the model's advScr1 / advScr2 /
+  // gAdv for theta and salt, a passive tracer's own (the tracers of a batch run concurrently)
   double *adv1, *adv2, *gAdv;
+  // the flow those passes advect by, transports and CFL numbers alike: uRes / vRes / wRes where
+  // the step has GM_AdvForm's residual flow (model.hip takes_res_flow), else uVel / vVel / wVel.
+  // The passes only: the right-hand side keeps Fields' velocity and its on-the-fly bolus terms
+  const double *advU, *advV, *advW;
 };
-// The Fields a passive tracer's kernels get: its own multi-dimensional scratch in place of the
-// model's (the bodies reach advScr1 / advScr2 / gAdv through these pointers only); both routes
-__host__ __device__ inline Fields ptr_fields(const Fields &f, const TracerArgs &a) {
-  Fields g = f;
-  g.advScr1 = a.adv1; g.advScr2 = a.adv2; g.gAdv = a.gAdv;
-  return g;
-}
-// The Fields GAD_ADVECTION's multi-dimensional passes get under GM_AdvForm: the residual flow in
-// place of the Eulerian velocity, transports and CFL numbers alike (k_gm_residual_flow has run)
-__host__ __device__ inline Fields res_flow_fields(const Fields &f) {
-  Fields g = f;
-  g.uVel = f.uRes; g.vVel = f.vRes; g.wVel = f.wRes;
-  return g;
-}
 // surfaceForcingPTr of a tracer with surface relaxation (ptracers_forcing_surf.F, the
 // experiment's own code/ form restated with parameters): evaluated left to right from the
 // tracer at the start of the step

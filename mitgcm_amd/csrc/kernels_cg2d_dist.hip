@@ -29,6 +29,7 @@
 // The width-1 EXCH_S3D_RL of r and s (cg2d.F:175,255,353) and EXCH_XY_RL of x (:135) are
 // the host's point-to-point exchange plus mgcm_exchange_field.
 #include "common.h"
+#include "launch.h"
 
 namespace mgcm {
 

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "launch.h"
 #include "phys.h"
 #include "rstar.h"
 #include <cstring>

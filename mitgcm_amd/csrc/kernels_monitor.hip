@@ -12,6 +12,7 @@
 // sequential over (k, j, i); the device's are trees, so the statistics agree to rounding
 // (tests/test_gpu_monitor.py: <= 1e-12 relative, min/max exact).
 #include "common.h"
+#include "launch.h"
 
 namespace mgcm {
 

@@ -20,9 +20,9 @@
 // DESIGN.md section 3.  The k-march forms and frames above 64 KiB stay functional (ptr_batch_ok).
 //
 // The tracers of a batch run concurrently, so each has its own gAdv / advScr1 / advScr2 / T* /
-// c' scratch (model.hip's third arena); the bodies reach the multi-dimensional scratch through
-// Fields pointers only (no arena-index addressing of those three), so a Fields copy with the
-// three pointers moved is enough.
+// c' scratch (model.hip's third arena).  A table entry is all a kernel knows of its tracer: the
+// bodies take the scratch, the GM/Redi switch and the flow the passes advect by from the
+// TracerArgs, and Params and Fields reach them as the model's.
 //
 // Included by kernels_step.hip (one translation unit with kernels_thermo.hip's bodies).
 #pragma once
@@ -43,14 +43,14 @@ __global__ void __launch_bounds__(256) k_ptr_adv_x(Dims d, Fields f, const Trace
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
-  adv_x_body(d, ptr_fields(f, a), a, b.lb);
+  adv_x_body(d, f, a, b.lb);
 }
 __global__ void __launch_bounds__(256) k_ptr_adv_y(Dims d, Fields f, const TracerArgs *__restrict__ tab,
                                                    const int *__restrict__ list, int nList, int nbPer) {
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
-  adv_y_body(d, ptr_fields(f, a), a, b.lb);
+  adv_y_body(d, f, a, b.lb);
 }
 // COMP: GAD_MULTIDIM_COMPRESSIBLE (the local volume in adv2); gen: the general form's loc is
 // adv1 (k_ptr_advg_plane), the lat-lon passes' is adv2 (k_ptr_adv_y) -- launch_tracer_step's
@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) k_ptr_adv_r(Dims d, Params p, Fields f, c
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
   const double *L = gen ? a.adv1 : a.adv2;
-  adv_r_body<COMP>(d, p, ptr_fields(f, a), a, L, COMP ? a.adv2 : L, b.lb);
+  adv_r_body<COMP>(d, p, f, a, L, COMP ? a.adv2 : L, b.lb);
 }
 
 // GAD_ADVECTION's general form (cube tiles and / or GAD_MULTIDIM_COMPRESSIBLE: the explicit
@@ -152,7 +152,7 @@ inline unsigned ptr_plane_threads(const Dims &d) {
 }
 
 // GAD_CALC_RHS + forcing + AB2 + TIMESTEP_TRACER of every tracer in `list`.  GM: the tracers
-// of the list take GM/Redi (PTRACERS_useGMRedi); a batch that mixes both kinds is two
+// of the list take GM/Redi (TracerArgs::gm; the host sorts them); a batch that mixes both kinds is two
 // launches (both bodies in one kernel spilled scalar registers to scratch).
 template <bool GM>
 __global__ void __launch_bounds__(256) k_ptr_rhs(Dims d, Params p, Fields f, const TracerArgs *__restrict__ tab,
@@ -161,9 +161,7 @@ __global__ void __launch_bounds__(256) k_ptr_rhs(Dims d, Params p, Fields f, con
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
-  const Fields g = ptr_fields(f, a);
-  p.useGMRedi = GM ? 1 : 0;
-  tracer_rhs_body<GM, true>(d, p, g, a, iterPtr, b.lb);
+  tracer_rhs_body<GM, true>(d, p, f, a, iterPtr, b.lb);
 }
 
 // GAD_IMPLICIT_R + SOLVE_TRIDIAGONAL + CYCLE_TRACER of every tracer in `list`
@@ -172,7 +170,6 @@ __global__ void __launch_bounds__(256) k_ptr_impl(Dims d, Params p, Fields f, co
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;   // (uniform over the workgroup: no barrier is skipped by part of it)
   const TracerArgs a = tab[list[b.it]];
-  p.useGMRedi = a.gm;
   tracer_impl_body<false>(d, p, f, a, nc, b.lb);
 }
 
@@ -193,28 +190,25 @@ bool ptr_batch_ok(const Dims &d, const Params &p, bool md) {
 // starting at lists + stride, its first nGM tracers the ones that take GM/Redi.  nLaunch (or
 // null): the kernel launches issued are added to it.  (The lists are all the kernels know of
 // who they step: theta and salt could join one with TracerArgs of their own.)
-// resFlow: the multi-dimensional passes advect by GM_AdvForm's residual flow (launch_tracer_step)
 hipError_t launch_ptracers_batch(const Dims &d, const Params &p, const Fields &f, const TracerArgs *tab, const int *lists,
-                                 int stride, int nMd, int nAll, int nGM, const int *iterPtr, hipStream_t s, int *nLaunch,
-                                 bool resFlow) {
+                                 int stride, int nMd, int nAll, int nGM, const int *iterPtr, hipStream_t s, int *nLaunch) {
   if (nAll <= 0) return hipSuccess;
   int nl = 0;
   const dim3 blk(MG_PLANE_THREADS);
   const int nbI = (int)mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr), nbF = (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
   if (nMd > 0) {
-    const Fields fm = resFlow ? res_flow_fields(f) : f;
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: the per-point X and Y passes
-      hipLaunchKernelGGL(k_ptr_adv_x, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, fm, tab, lists, nMd, nbF);
-      hipLaunchKernelGGL(k_ptr_adv_y, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, fm, tab, lists, nMd, nbI);
-      hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 0);
+      hipLaunchKernelGGL(k_ptr_adv_x, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbF);
+      hipLaunchKernelGGL(k_ptr_adv_y, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbI);
+      hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 0);
       nl += 3;
     } else {                // the general form: every pass of a level in one workgroup
       if (ptr_plane_lds(d, p) > MG_PTR_PLANE_LDS_MAX) return hipErrorInvalidValue;   // (ptr_batch_ok was not asked)
       hipLaunchKernelGGL(k_ptr_advg_plane, dim3((unsigned)(d.nT * d.Nr * nMd)), dim3(ptr_plane_threads(d)), ptr_plane_lds(d, p), s,
-                         d, fm, tab, lists, nMd, (int)cube, (int)comp);
-      if (comp) hipLaunchKernelGGL(k_ptr_adv_r<true>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 1);
-      else hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, fm, tab, lists, nMd, nbI, 1);
+                         d, f, tab, lists, nMd, (int)cube, (int)comp);
+      if (comp) hipLaunchKernelGGL(k_ptr_adv_r<true>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
+      else hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
       nl += 2;
     }
   }

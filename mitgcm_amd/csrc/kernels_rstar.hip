@@ -10,6 +10,7 @@
 // source (srcOf, the EXCH map of the tile topology) inside the same pass, because
 // EXCH copies values that are computed by the same expression as the source's.
 #include "common.h"
+#include "launch.h"
 #include "phys.h"
 #include "rstar.h"
 #include "ucg2d.h"

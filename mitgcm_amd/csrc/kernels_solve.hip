@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "cg2d.h"
+#include "launch.h"
 #include "gm_tensor.h"
 
 namespace mgcm {

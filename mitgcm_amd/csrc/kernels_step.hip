@@ -22,6 +22,7 @@
 // Every body is the same device function the separate kernels run, so the results are the
 // same bits.  The two source files are included rather than linked: hipcc builds without
 // relocatable device code, and the fused kernels need both files' bodies.
+#include "launch.h"
 #include "kernels_dyn.hip"
 #include "kernels_thermo.hip"
 #include "ucg2d.h"
@@ -219,7 +220,10 @@ hipError_t launch_gm_phi(const Dims &d, const Params &p, const Fields &f, hipStr
 
 // Both tracers of THERMODYNAMICS in two launches instead of four (small grids, outside the
 // fold, e.g. after the pressure solve in the staggered step): [rhs(theta) | rhs(salt)], then
-// [implicit solve (theta) | (salt)]; theta's T* in gTscr, salt's in cpScr
+// [implicit solve (theta) | (salt)]; theta's T* in gTscr, salt's in cpScr.
+// The paired launch here and the fold (launch_dyn_thermo) choose their GM template from
+// p.useGMRedi, not from TracerArgs::gm: one template serves both tracers of a grid, and only
+// theta and salt reach them, whose gm is p.useGMRedi.  The bodies inside read a.gm as everywhere.
 template <bool GM>
 __global__ void __launch_bounds__(256) k_tr_rhs_pair(Dims d, Params p, Fields f, TracerArgs aT, TracerArgs aS,
                                                      const int *iterPtr, int nbTr) {

@@ -23,6 +23,7 @@
 // the interior is produced: the halo of theta is refilled by the end-of-step
 // EXCH (do_fields_blocking_exchanges.F).
 #include "common.h"
+#include "launch.h"
 #include "phys.h"
 #include "gm_tensor.h"
 
@@ -152,10 +153,10 @@ __device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const
   double v = T[q3];
   if (i >= 2 - d.OLx && i <= d.sNx + d.OLx - 1) {
     const double drF = f.drF[k - 1], dT = a.dT;
-    auto uTr = [&](int ii) { return f.uVel[MG_I3(d, ii, j, k, t)] * (f.dyG[MG_I2(d, ii, j, t)] * drF * f.hFacW[MG_I3(d, ii, j, k, t)]); };
+    auto uTr = [&](int ii) { return a.advU[MG_I3(d, ii, j, k, t)] * (f.dyG[MG_I2(d, ii, j, t)] * drF * f.hFacW[MG_I3(d, ii, j, k, t)]); };
     auto afx = [&](int ii) {   // zero at i = 1-OLx, 2-OLx, sNx+OLx
       if (ii < 3 - d.OLx || ii > d.sNx + d.OLx - 1) return 0.0;
-      const double cfl = fabs(f.uVel[MG_I3(d, ii, j, k, t)] * dT * f.recip_dxC[MG_I2(d, ii, j, t)]);
+      const double cfl = fabs(a.advU[MG_I3(d, ii, j, k, t)] * dT * f.recip_dxC[MG_I2(d, ii, j, t)]);
       return dst3fl_h(uTr(ii), cfl, T[MG_I3(d, ii - 2, j, k, t)], T[MG_I3(d, ii - 1, j, k, t)], T[MG_I3(d, ii, j, k, t)],
                       T[MG_I3(d, ii + 1, j, k, t)], f.maskW[MG_I3(d, ii - 1, j, k, t)], f.maskW[MG_I3(d, ii, j, k, t)],
                       f.maskW[MG_I3(d, ii + 1, j, k, t)], a.limiter);
@@ -164,7 +165,7 @@ __device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const
     v = v - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
                 (afx(i + 1) - afx(i) - T[q3] * (uTr(i + 1) - uTr(i))) * f.maskInC[q];
   }
-  f.advScr1[q3] = v;
+  a.adv1[q3] = v;
 }
 __global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) { adv_x_body(d, f, a, mg_xcd_block()); }
 
@@ -174,19 +175,19 @@ __device__ __forceinline__ void adv_y_body(const Dims &d, const Fields &f, const
   MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx || j > d.sNy) return;
-  const double *__restrict__ L1 = f.advScr1;
+  const double *__restrict__ L1 = a.adv1;
   const long q3 = MG_I3(d, i, j, k, t);
   const double drF = f.drF[k - 1], dT = a.dT;
-  auto vTr = [&](int jj) { return f.vVel[MG_I3(d, i, jj, k, t)] * (f.dxG[MG_I2(d, i, jj, t)] * drF * f.hFacS[MG_I3(d, i, jj, k, t)]); };
+  auto vTr = [&](int jj) { return a.advV[MG_I3(d, i, jj, k, t)] * (f.dxG[MG_I2(d, i, jj, t)] * drF * f.hFacS[MG_I3(d, i, jj, k, t)]); };
   auto afy = [&](int jj) {   // zero at j = 1-OLy, 2-OLy, sNy+OLy
     if (jj < 3 - d.OLy || jj > d.sNy + d.OLy - 1) return 0.0;
-    const double cfl = fabs(f.vVel[MG_I3(d, i, jj, k, t)] * dT * f.recip_dyC[MG_I2(d, i, jj, t)]);
+    const double cfl = fabs(a.advV[MG_I3(d, i, jj, k, t)] * dT * f.recip_dyC[MG_I2(d, i, jj, t)]);
     return dst3fl_h(vTr(jj), cfl, L1[MG_I3(d, i, jj - 2, k, t)], L1[MG_I3(d, i, jj - 1, k, t)], L1[MG_I3(d, i, jj, k, t)],
                     L1[MG_I3(d, i, jj + 1, k, t)], f.maskS[MG_I3(d, i, jj - 1, k, t)], f.maskS[MG_I3(d, i, jj, k, t)],
                     f.maskS[MG_I3(d, i, jj + 1, k, t)], a.limiter);
   };
   const long q = MG_I2(d, i, j, t);
-  f.advScr2[q3] = L1[q3] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
+  a.adv2[q3] = L1[q3] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
                                (afy(j + 1) - afy(j) - a.tr[q3] * (vTr(j + 1) - vTr(j))) * f.maskInC[q];
 }
 __global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) { adv_y_body(d, f, a, mg_xcd_block()); }
@@ -205,14 +206,14 @@ __device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const
   const double rA = f.rA[q], dT = a.dT;
 #define MC(kk) f.maskC[MG_I3(d, i, j, kk, t)]
 #define LT(kk) L2[MG_I3(d, i, j, kk, t)]
-  auto rtr = [&](int kk) { return (kk <= 1 || kk > Nr) ? 0.0 : f.wVel[MG_I3(d, i, j, kk, t)] * rA * MC(kk - 1); };
+  auto rtr = [&](int kk) { return (kk <= 1 || kk > Nr) ? 0.0 : a.advW[MG_I3(d, i, j, kk, t)] * rA * MC(kk - 1); };
   auto fver = [&](int kk) {   // fVerT through the top of level kk, 0 at kk = 1 and below Nr
     if (kk <= 1 || kk > Nr) return 0.0;
     const int km2 = kk - 2 > 1 ? kk - 2 : 1, km1 = kk - 1 > 1 ? kk - 1 : 1, kp1 = kk + 1 < Nr ? kk + 1 : Nr;
     const double Rjp = (LT(kk) - LT(kp1)) * MC(kp1);
     const double Rj = (LT(km1) - LT(kk)) * MC(kk) * MC(km1);
     const double Rjm = (LT(km2) - LT(km1)) * MC(km1);
-    const double cfl = fabs(f.wVel[MG_I3(d, i, j, kk, t)] * dT * f.recip_drC[kk - 1]);
+    const double cfl = fabs(a.advW[MG_I3(d, i, j, kk, t)] * dT * f.recip_drC[kk - 1]);
     const double oneSixth = 1.0 / 6.0;
     const double d0 = (2.0 - cfl) * (1.0 - cfl) * oneSixth, d1 = (1.0 - cfl * cfl) * oneSixth;
     const double rT = rtr(kk);
@@ -228,11 +229,11 @@ __device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const
   if (COMP) {
     const double tmpTrac = LT(k) * V[q3] - dT * (fDn - fUp) * p.rkSign * f.maskInC[q];
     const double lv = V[q3] - dT * (rTransKp - rTrans) * p.rkSign * f.maskInC[q];
-    f.gAdv[q3] = (tmpTrac - a.tr[q3] * lv) * f.recip_rA[q] * f.recip_drF[k - 1] * f.recip_hFacC[q3] / dT;
+    a.gAdv[q3] = (tmpTrac - a.tr[q3] * lv) * f.recip_rA[q] * f.recip_drF[k - 1] * f.recip_hFacC[q3] / dT;
   } else {
     const double lt = LT(k) - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
                                   (fDn - fUp - a.tr[q3] * (rTransKp - rTrans)) * p.rkSign * f.maskInC[q];
-    f.gAdv[q3] = (lt - a.tr[q3]) / dT;
+    a.gAdv[q3] = (lt - a.tr[q3]) / dT;
   }
 #undef MC
 #undef LT
@@ -248,8 +249,10 @@ __global__ void __launch_bounds__(256) k_adv_r(Dims d, Params p, Fields f, Trace
 // direction and overlap-only / interior-only updates depend on the tile's face, :339-367,
 // with FILL_CS_CORNER_TR_RL around the overlap-only fluxes and FILL_CS_CORNER_UV_RS on the
 // masks) and/or GAD_MULTIDIM_COMPRESSIBLE (the local volume carried through the passes).
-// The passes run as explicit steps over the whole slab: loc (advScr1) and vol (advScr2)
-// are updated in place, the face fluxes of a pass go to gTscr (free until k_tracer_rhs).
+// The passes run as explicit steps over the whole slab: loc (the tracer's adv1) and vol (adv2)
+// are updated in place, the face fluxes of a pass go to the model's gTscr (free until
+// k_tracer_rhs): only the functional route runs these kernels, one tracer after another, so the
+// flux frame is not the tracer's own (the batched route keeps it in LDS, k_ptr_advg_plane).
 struct AdvCfg { bool ov, in, cx, cy; };
 __device__ __forceinline__ AdvCfg adv_cfg(bool cube, int face, int ipass) {
   AdvCfg c{false, false, false, false};
@@ -297,7 +300,7 @@ __device__ __forceinline__ double mask_loc(const Dims &d, const Fields &f, bool 
 
 // The passes' arithmetic as device functions of one point of one level's frame: L (loc), V
 // (vol) and G (the face fluxes of the current stage) point at the frame's (1-OLx, 1-OLy)
-// corner, nx doubles per row -- a level of advScr1 / advScr2 / gTscr for the explicit-pass
+// corner, nx doubles per row -- a level of a.adv1 / a.adv2 / gTscr for the explicit-pass
 // kernels below, LDS for the plane kernel (k_ptr_advg_plane, kernels_ptracers.hip).  One
 // statement of the maths for both.
 #define MG_FR(d, i, j) ((i) + (d).OLx - 1 + ((j) + (d).OLy - 1) * (d).nx)
@@ -344,14 +347,14 @@ __device__ __forceinline__ void advg_flux_point(const Dims &d, const Fields &f, 
   const double dT = a.dT, drF = f.drF[k - 1];
   double af = 0.0;
   if (!ydir && i >= 3 - d.OLx && i <= d.sNx + d.OLx - 1) {
-    const double uTr = f.uVel[q3] * (f.dyG[MG_I2(d, i, j, t)] * drF * f.hFacW[q3]);
-    const double cfl = fabs(f.uVel[q3] * dT * f.recip_dxC[MG_I2(d, i, j, t)]);
+    const double uTr = a.advU[q3] * (f.dyG[MG_I2(d, i, j, t)] * drF * f.hFacW[q3]);
+    const double cfl = fabs(a.advU[q3] * dT * f.recip_dxC[MG_I2(d, i, j, t)]);
     af = dst3fl_h(uTr, cfl, Lc[MG_FR(d, i - 2, j)], Lc[MG_FR(d, i - 1, j)], Lc[q], Lc[MG_FR(d, i + 1, j)],
                   mask_loc(d, f, cube, edges, true, i - 1, j, k, t), mask_loc(d, f, cube, edges, true, i, j, k, t),
                   mask_loc(d, f, cube, edges, true, i + 1, j, k, t), a.limiter);
   } else if (ydir && j >= 3 - d.OLy && j <= d.sNy + d.OLy - 1) {
-    const double vTr = f.vVel[q3] * (f.dxG[MG_I2(d, i, j, t)] * drF * f.hFacS[q3]);
-    const double cfl = fabs(f.vVel[q3] * dT * f.recip_dyC[MG_I2(d, i, j, t)]);
+    const double vTr = a.advV[q3] * (f.dxG[MG_I2(d, i, j, t)] * drF * f.hFacS[q3]);
+    const double cfl = fabs(a.advV[q3] * dT * f.recip_dyC[MG_I2(d, i, j, t)]);
     af = dst3fl_h(vTr, cfl, Lc[MG_FR(d, i, j - 2)], Lc[MG_FR(d, i, j - 1)], Lc[q], Lc[MG_FR(d, i, j + 1)],
                   mask_loc(d, f, cube, edges, false, i, j - 1, k, t), mask_loc(d, f, cube, edges, false, i, j, k, t),
                   mask_loc(d, f, cube, edges, false, i, j + 1, k, t), a.limiter);
@@ -393,8 +396,8 @@ __device__ __forceinline__ void advg_upd_point(const Dims &d, const Fields &f, c
   const long q3n = ydir ? MG_I3(d, i, j + 1, k, t) : MG_I3(d, i + 1, j, k, t);
   const double dF = G[fqn] - G[fq];
   double dU;
-  if (ydir) dU = f.vVel[q3n] * (f.dxG[MG_I2(d, i, j + 1, t)] * drF * f.hFacS[q3n]) - f.vVel[q3] * (f.dxG[q] * drF * f.hFacS[q3]);
-  else dU = f.uVel[q3n] * (f.dyG[MG_I2(d, i + 1, j, t)] * drF * f.hFacW[q3n]) - f.uVel[q3] * (f.dyG[q] * drF * f.hFacW[q3]);
+  if (ydir) dU = a.advV[q3n] * (f.dxG[MG_I2(d, i, j + 1, t)] * drF * f.hFacS[q3n]) - a.advV[q3] * (f.dxG[q] * drF * f.hFacS[q3]);
+  else dU = a.advU[q3n] * (f.dyG[MG_I2(d, i + 1, j, t)] * drF * f.hFacW[q3n]) - a.advU[q3] * (f.dyG[q] * drF * f.hFacW[q3]);
   if (comp) {
     const double tmpTrac = L[fq] * V[fq] - dT * dF * f.maskInC[q];
     const double vol = V[fq] - dT * dU * f.maskInC[q];
@@ -406,28 +409,29 @@ __device__ __forceinline__ void advg_upd_point(const Dims &d, const Fields &f, c
 }
 
 // the explicit-pass kernels: one thread per frame point (per corner point: k_advg_fill), the
-// frames being level k of tile t of advScr1 / advScr2 / gTscr
+// frames being level k of tile t of a.adv1 / a.adv2 / gTscr (k_advg_fill, which has no
+// TracerArgs, gets loc as an argument)
 #define MG_LEVEL(p, d, k, t) ((p) + (long)((k) - 1) * (d).n2 + (long)(t) * (d).n3)
 __global__ void __launch_bounds__(256) k_advg_init(Dims d, Fields f, TracerArgs a, int comp) {
   MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
-  advg_init_point(d, f, a, comp != 0, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t), MG_LEVEL(f.advScr2, d, k, t));
+  advg_init_point(d, f, a, comp != 0, i, j, k, t, MG_LEVEL(a.adv1, d, k, t), MG_LEVEL(a.adv2, d, k, t));
 }
-__global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, int ipass, int stage) {
+__global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, double *loc, int ipass, int stage) {
   const int per = 4 * d.OLx * d.OLy;
   const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (long)per * d.nT * d.Nr) return;
   const int c = (int)(g % per), z = (int)(g / per);
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  advg_fill_point(d, f.tileFace[t], f.tileEdge[t], ipass, stage, c, MG_LEVEL(f.advScr1, d, k, t));
+  advg_fill_point(d, f.tileFace[t], f.tileEdge[t], ipass, stage, c, MG_LEVEL(loc, d, k, t));
 }
 __global__ void __launch_bounds__(256) k_advg_flux(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube) {
   MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
   const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
-  advg_flux_point(d, f, a, ipass, ydir, cube != 0, face, edges, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t),
+  advg_flux_point(d, f, a, ipass, ydir, cube != 0, face, edges, i, j, k, t, MG_LEVEL(a.adv1, d, k, t),
                   MG_LEVEL(f.gTscr, d, k, t));
 }
 __global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube, int comp) {
@@ -435,8 +439,8 @@ __global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
   const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
-  advg_upd_point(d, f, a, ipass, ydir, cube != 0, comp != 0, face, edges, i, j, k, t, MG_LEVEL(f.advScr1, d, k, t),
-                 MG_LEVEL(f.advScr2, d, k, t), MG_LEVEL(f.gTscr, d, k, t));
+  advg_upd_point(d, f, a, ipass, ydir, cube != 0, comp != 0, face, edges, i, j, k, t, MG_LEVEL(a.adv1, d, k, t),
+                 MG_LEVEL(a.adv2, d, k, t), MG_LEVEL(f.gTscr, d, k, t));
 }
 
 // tracer_rhs_body with its operands loaded behind the reference's conditions: the form the
@@ -576,7 +580,7 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
   const double fVerUp = fvert(k, rTrans), fVerDn = fvert(k + 1, rTransKp);
   const double fZi = fzon(i), fZe = fzon(i + 1);
   const double fMi = fmer(j), fMn = fmer(j + 1);
-  const double g0 = a.multiDim ? f.gAdv[q3] : 0.0;
+  const double g0 = a.multiDim ? a.gAdv[q3] : 0.0;
   double gT = g0 - f.recip_hFacC[q3] * f.recip_drF[k - 1] * recip_rA *
                        ((fZe - fZi) * maskInC + (fMn - fMi) * maskInC + (fVerDn - fVerUp) * p.rkSign -
                         Tk * ((uT1 - uT0) * advFac + (vT1 - vT0) * advFac + (rTransKp - rTrans) * rAdvFac) * maskInC);
@@ -807,7 +811,7 @@ __device__ __forceinline__ void tracer_rhs_body(const Dims &d, const Params &p, 
   const double fVerUp = fvert(k, rTrans), fVerDn = fvert(k + 1, rTransKp);
   const double fZi = fzon(i), fZe = fzon(i + 1);
   const double fMi = fmer(j), fMn = fmer(j + 1);
-  const double g0 = a.multiDim ? f.gAdv[q3] : 0.0;
+  const double g0 = a.multiDim ? a.gAdv[q3] : 0.0;
   double gT = g0 - f.recip_hFacC[q3] * f.recip_drF[k - 1] * recip_rA *
                        ((fZe - fZi) * maskInC + (fMn - fMi) * maskInC + (fVerDn - fVerUp) * p.rkSign -
                         Tk * ((uT1 - uT0) * advFac + (vT1 - vT0) * advFac + (rTransKp - rTrans) * rAdvFac) * maskInC);
@@ -950,7 +954,7 @@ __device__ __forceinline__ double tracer_flat_point(const Dims &d, const Params 
   o.ivd0 = f.IVDConvCount[q3]; o.ivd1 = f.IVDConvCount[q3 + dkd];
   TrCol c;
   tracer_load_col(d, f, a, q, c);
-  o.rhC = f.recip_hFacC[q3]; o.gAdv = f.gAdv[q3]; o.gOld = a.gNm1[q3];
+  o.rhC = f.recip_hFacC[q3]; o.gAdv = a.gAdv[q3]; o.gOld = a.gNm1[q3];
   double gN = 0.0;
   const double v = tracer_flat_arith(p, f, a, Nr, k, myIter, c, o, &gN);
   if (a.useAB) a.gNm1[q3] = gN;
@@ -999,7 +1003,7 @@ __global__ void __launch_bounds__(256) TRM_ATTR k_tracer_march(Dims d, Params p,
     o.Tw = T[q3 - 1]; o.Te = T[q3 + 1]; o.Ts = T[q3 - nx]; o.Tn = T[q3 + nx];
     o.u0 = f.uVel[q3]; o.u1 = f.uVel[q3 + 1]; o.v0 = f.vVel[q3]; o.v1 = f.vVel[q3 + nx];
     o.hW0 = f.hFacW[q3]; o.hW1 = f.hFacW[q3 + 1]; o.hS0 = f.hFacS[q3]; o.hS1 = f.hFacS[q3 + nx];
-    o.rhC = f.recip_hFacC[q3]; o.gAdv = a.multiDim ? f.gAdv[q3] : 0.0; o.gOld = a.useAB ? a.gNm1[q3] : 0.0;
+    o.rhC = f.recip_hFacC[q3]; o.gAdv = a.multiDim ? a.gAdv[q3] : 0.0; o.gOld = a.useAB ? a.gNm1[q3] : 0.0;
     double gN = 0.0;
     const double v = tracer_flat_arith(p, f, a, Nr, k, myIter, c, o, &gN);
     if (a.useAB) a.gNm1[q3] = gN;
@@ -1115,7 +1119,7 @@ __global__ void __launch_bounds__(256) TRM_ATTR k_tracer_march2(Dims d, Params p
     const double u2 = f.uVel[q3 + 2], hW2 = f.hFacW[q3 + 2];
     const trd2 hW01 = L2(f.hFacW, q3), hS0 = L2(f.hFacS, q3), hS1 = L2(f.hFacS, q3 + nx);
     const trd2 rhC = L2(f.recip_hFacC, q3);
-    const trd2 gA = a.multiDim ? L2(f.gAdv, q3) : trd2{0.0, 0.0};
+    const trd2 gA = a.multiDim ? L2(a.gAdv, q3) : trd2{0.0, 0.0};
     const trd2 gO = a.useAB ? L2(a.gNm1, q3) : trd2{0.0, 0.0};
     double v[2], gN[2] = {0.0, 0.0}, cpo[2] = {0.0, 0.0};
 #pragma unroll
@@ -1216,7 +1220,7 @@ __device__ __forceinline__ void tracer_impl_body(const Dims &d, const Params &p,
     // KappaRT = (IVDConvCount*ivdc_kappa + BL79(=0)) + diffKrNr [+ Kwz*maskInC] (calc_3d_diffusivity.F)
     auto kappa = [&](double ivd, double kwz) {
       double kap = (ivd * p.ivdc_kappa + 0.0) + a.diffKr;
-      if (p.useGMRedi) kap = kap + kwz * mIn;
+      if (a.gm) kap = kap + kwz * mIn;
       return kap;
     };
     if constexpr (!UL) MG_COLF_K(k) {
@@ -1227,10 +1231,10 @@ __device__ __forceinline__ void tracer_impl_body(const Dims &d, const Params &p,
       double sub = 0.0, sup = 0.0;
       if (k >= 2)
         sub = -(p.deltaTtracer * G3(maskC, i, j, k - 1) * rh * rdrF *
-                kappa(G3(IVDConvCount, i, j, k), p.useGMRedi ? G3(Kwz, i, j, k) : 0.0) * f.recip_drC[k - 1]);
+                kappa(G3(IVDConvCount, i, j, k), a.gm ? G3(Kwz, i, j, k) : 0.0) * f.recip_drC[k - 1]);
       if (k <= Nr - 1)
         sup = -(p.deltaTtracer * G3(maskC, i, j, k + 1) * rh * rdrF *
-                kappa(G3(IVDConvCount, i, j, k + 1), p.useGMRedi ? G3(Kwz, i, j, k + 1) : 0.0) * f.recip_drC[k]);
+                kappa(G3(IVDConvCount, i, j, k + 1), a.gm ? G3(Kwz, i, j, k + 1) : 0.0) * f.recip_drC[k]);
       sSub[me] = sub;
       sSup[me] = sup;
       sY[me] = a.scr[q3];
@@ -1244,7 +1248,7 @@ __device__ __forceinline__ void tracer_impl_body(const Dims &d, const Params &p,
       const double rhc = f.recip_hFacC[q3], y = a.scr[q3];
       const double mM = G3(maskC, i, j, km), mP = G3(maskC, i, j, kp);
       const double ivK = G3(IVDConvCount, i, j, k), ivP = G3(IVDConvCount, i, j, kp);
-      const double kwK = p.useGMRedi ? G3(Kwz, i, j, k) : 0.0, kwP = p.useGMRedi ? G3(Kwz, i, j, kp) : 0.0;
+      const double kwK = a.gm ? G3(Kwz, i, j, k) : 0.0, kwP = a.gm ? G3(Kwz, i, j, kp) : 0.0;
       const double rdrF = f.recip_drF[k - 1], rdcK = f.recip_drC[k - 1], rdcP = f.recip_drC[kp - 1];
       const double rh = rs ? rhc / rsx : rhc;
       double sub = 0.0, sup = 0.0;
@@ -1315,7 +1319,6 @@ hipError_t launch_gm_residual_flow(const Dims &d, const Params &p, const Fields 
   return hipGetLastError();
 }
 
-hipError_t launch_phys_ring(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s);
 // the 16-byte form (k_oceanic_phys2) or the per-point one
 static bool phys_v2(const Dims &d, const Params &p, const Fields &f) {
   auto al = [](const void *q) { return ((uintptr_t)q & 15u) == 0; };
@@ -1372,44 +1375,43 @@ static bool tracer_march_on(const Dims &d) {
 
 // impl = false: the right-hand side only (the implicit solve is launched by the caller)
 // nLaunch (or null): the kernel launches issued are added to it, counted where they are issued
-// resFlow: GM_AdvForm's residual flow is in uRes / vRes / wRes (launch_gm_residual_flow) and the
-// multi-dimensional passes advect by it; the right-hand side keeps f (a multi-dimensional tracer
-// takes only the Redi diffusion there, a scheme-2 tracer forms the bolus terms on the fly)
-hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f0, const TracerArgs &a, const int *iterPtr,
-                              hipStream_t s, bool impl, int *nLaunch, bool resFlow) {
+// Who is stepped is all in `a`: its GM/Redi switch (a.gm, not p.useGMRedi), its multi-dimensional
+// scratch and the flow the passes advect by (a.advU / V / W: GM_AdvForm's residual flow where
+// launch_gm_residual_flow has run).  The right-hand side keeps f's velocity: a multi-dimensional
+// tracer takes only the Redi diffusion there, a scheme-2 tracer forms the bolus terms on the fly
+hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a, const int *iterPtr,
+                              hipStream_t s, bool impl, int *nLaunch) {
   struct Count { int n, *out; ~Count() { if (out) *out += n; } } cnt{0, nLaunch};
 #define MG_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); cnt.n++; } while (0)
   const dim3 blk(MG_PLANE_THREADS), grd(mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr));
-  const Fields &f = f0;
   if (a.multiDim) {
-    const Fields f = resFlow ? res_flow_fields(f0) : f0;   // (the passes only)
     const dim3 fgrd(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr));
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: fused per-point X and Y passes
       MG_LAUNCH(k_adv_x, fgrd, blk, 0, s, d, f, a);
       MG_LAUNCH(k_adv_y, grd, blk, 0, s, d, f, a);
-      MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr2, f.advScr2);
+      MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, a.adv2, a.adv2);
     } else {                // the general form: explicit passes over the whole slab
       MG_LAUNCH(k_advg_init, fgrd, blk, 0, s, d, f, a, (int)comp);
       const unsigned cgrd = (unsigned)((4L * d.OLx * d.OLy * d.nT * d.Nr + 255) / 256);
       for (int ipass = 1; ipass <= (cube ? 3 : 2); ipass++)
         for (int ydir = 0; ydir < 2; ydir++) {
-          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir);
+          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, a.adv1, ipass, 2 * ydir);
           MG_LAUNCH(k_advg_flux, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube);
-          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, ipass, 2 * ydir + 1);
+          if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, a.adv1, ipass, 2 * ydir + 1);
           MG_LAUNCH(k_advg_upd, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube, (int)comp);
         }
-      if (comp) MG_LAUNCH(k_adv_r<true>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr2);
-      else MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, f.advScr1, f.advScr1);
+      if (comp) MG_LAUNCH(k_adv_r<true>, grd, blk, 0, s, d, p, f, a, a.adv1, a.adv2);
+      else MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, a.adv1, a.adv1);
     }
   }
   // GM/Redi fluxes as a template switch: without them the kernel holds half the registers
   // a passive tracer with forcing of its own (pkg/ptracers): the generic body's PTR form, whose
   // arithmetic is the flat and marching forms' (they are bit-identical restatements of it)
   const bool ptrForc = a.relaxRate != 0.0 || a.src != 0.0;
-  if (ptrForc && p.useGMRedi) MG_LAUNCH((k_tracer_rhs<true, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
+  if (ptrForc && a.gm) MG_LAUNCH((k_tracer_rhs<true, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (ptrForc) MG_LAUNCH((k_tracer_rhs<false, true>), grd, blk, 0, s, d, p, f, a, iterPtr);
-  else if (p.useGMRedi) MG_LAUNCH(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
+  else if (a.gm) MG_LAUNCH(k_tracer_rhs<true>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (a.scheme != 2 || p.useAB3)   // U3 / C4 and ADAMS_BASHFORTH3: the generic body only
     MG_LAUNCH(k_tracer_rhs<false>, grd, blk, 0, s, d, p, f, a, iterPtr);
   else if (tracer_march_on(d)) {
@@ -1427,11 +1429,11 @@ hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f0, 
     const int hx = d.sNx / 2;
     if (m2Env != 0 && (d.sNx & 1) == 0 && (d.OLx & 1) == 0 && (d.nx & 1) == 0 && (d.n3 & 1) == 0 && hx <= 256 && al(a.tr) &&
         al(a.trNext) && al(a.scr) && al(a.gNm1) && al(f.maskC) && al(f.wVel) && al(f.IVDConvCount) && al(f.uVel) &&
-        al(f.vVel) && al(f.hFacW) && al(f.hFacS) && al(f.recip_hFacC) && (!a.multiDim || al(f.gAdv))) {
+        al(f.vVel) && al(f.hFacW) && al(f.hFacS) && al(f.recip_hFacC) && (!a.multiDim || al(a.gAdv))) {
       const int TY = 256 / hx, nty2 = (d.sNy + TY - 1) / TY;
       // the implicit solve inside a whole-column march (tracer_fwd_form): no T* round trip
       const int fwd = tracer_fwd_form(d);
-      if (impl && p.implicitDiffusion && !p.useGMRedi && fwd && !a.multiDim && a.cp && al(a.cp) && d.Nr > 1) {
+      if (impl && p.implicitDiffusion && !a.gm && fwd && !a.multiDim && a.cp && al(a.cp) && d.Nr > 1) {
         if (fwd == 3) {
           if (m2Env == 2) {   // flat: the column pairs dealt evenly over one workgroup per CU
             static int nCU = 0;

@@ -19,6 +19,7 @@
 
 #include "../../include/mitgcm_amd.h"
 #include "cg2d.h"
+#include "launch.h"
 
 namespace mgcm {
 // Host ranges the Fortran mirror registered for DMA (fortran_abi.hip register_host: the
@@ -49,64 +50,6 @@ hipError_t mg_host_copy(void *dst, const void *src, size_t bytes, hipMemcpyKind 
   }
   return hipSuccess;
 }
-}  // namespace mgcm
-
-namespace mgcm {
-hipError_t launch_mom_step(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool ring = true);
-bool mom_ring_separable(const Dims &, const Params &);
-hipError_t launch_mom_ring(const Dims &, const Params &, const Fields &, const int *, hipStream_t);
-hipError_t launch_phi_hyd(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_sfp_rhs(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_exchange(const Dims &, double *, const long *, int, int, hipStream_t);
-hipError_t launch_cgd(const Dims &, const Params &, const Fields &, int, double, double *, hipStream_t);
-hipError_t launch_cgd_record(SolveRecord *, const int *, double, double, double, double, int, double, int, hipStream_t);
-hipError_t launch_field_pack(double *, const long *, long, double *, int, hipStream_t);
-hipError_t launch_correction(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_bump_counter(int *, int, hipStream_t);
-hipError_t launch_exchange_multi(const Dims &, const XFields &, const long *, int, int *, hipStream_t);
-hipError_t launch_exchange_uv(const Dims &, double *, double *, const long *, int, int, int, hipStream_t);
-hipError_t launch_exchange_mixed(const Dims &, double *, double *, int, const long *, int, int, const XFields &,
-                                 const long *, int, int *, hipStream_t);
-hipError_t launch_exchange_uv_pairs(const Dims &, double *const *, double *const *, int, const long *, int, int,
-                                   hipStream_t);
-hipError_t launch_exch_eta(const Dims &, const Params &, const Fields &, const long *, bool, int, hipStream_t,
-                           int fromX = 0);
-hipError_t launch_corr_cont(const Dims &, const Params &, const Fields &, int, hipStream_t, const long *etaSrc = nullptr,
-                            bool gmNext = false);
-hipError_t launch_calc_r_star(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool fuseEtaH = false,
-                              int fromX = 0);
-hipError_t launch_rstar_exmix(const Dims &, const Params &, const Fields &, const long *, bool, int, double *, double *, int,
-                              const long *, int, int, const XFields &, const long *, int, hipStream_t);
-hipError_t launch_rstar_exch(const Dims &, const Params &, const Fields &, const long *, bool, const XFields &, const long *,
-                             int, int *, hipStream_t, int fromX = 0, int empNext = 0);
-hipError_t launch_update_r_star_cg2d(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool sfp = false,
-                                     bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr,
-                                     bool keepFac = false);
-hipError_t launch_halo_pack(const Dims &, const XFields &, const long *, long, double *, int, hipStream_t);
-bool phys_ring_ok(const Dims &, const Params &, const Fields &);
-hipError_t launch_oceanic_phys(const Dims &, const Params &, const Fields &, const int *, hipStream_t, bool gm = true,
-                               bool ring = false);
-hipError_t launch_tracer_step(const Dims &, const Params &, const Fields &, const TracerArgs &, const int *, hipStream_t,
-                              bool impl = true, int *nLaunch = nullptr, bool resFlow = false);
-bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
-hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
-                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true);
-bool phi_pipe_ok(const Dims &, const Params &);
-hipError_t launch_phi_del2(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, const long *, const XFields &, const long *, int,
-                                 int *, hipStream_t, int fromX, int empNext);
-bool dyn_thermo_takes_gm(const Params &);
-hipError_t launch_gm_tensor(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_gm_residual_flow(const Dims &, const Params &, const Fields &, hipStream_t);
-bool gm_phi_fusable(const Dims &, const Params &);
-hipError_t launch_gm_phi(const Dims &, const Params &, const Fields &, hipStream_t, bool op = false);
-bool tracer_hpair_ok(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
-hipError_t launch_tracer_hpair(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &,
-                               const int *, hipStream_t);
-hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, hipStream_t);
-bool ptr_batch_ok(const Dims &, const Params &, bool md);
-hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int, int, int,
-                                 int, const int *, hipStream_t, int *nLaunch = nullptr, bool resFlow = false);
 }  // namespace mgcm
 
 using namespace mgcm;
@@ -1722,6 +1665,39 @@ int mgcm_dynamics(mgcm_model *m) {
   return dynamics_on(m, true);
 }
 
+// gad_init_fixed.F:126-162: multi-dimensional advection for the schemes that are not
+// Adams-Bashforth ones; AB (2 or 3) on the tendency for C2, U3 and C4
+static bool scheme_is_ab(int scheme) { return scheme == 2 || scheme == 3 || scheme == 4; }
+static bool scheme_multi_dim(const Params &p, int advection, int scheme) {
+  return p.multiDimAdvection && advection && !scheme_is_ab(scheme);
+}
+// Whether this model's THERMODYNAMICS takes GM_AdvForm's residual flow (k_gm_residual_flow ->
+// uRes, vRes, wRes): some stepped tracer -- theta, salt or a passive one -- is multi-dimensional.
+// From the parameters alone: plan_step launches the kernel by it (StepPlan::resFlow) and the two
+// builders below point every tracer's passes at the flow by it.
+static bool takes_res_flow(const mgcm_model *m) {
+  const Params &p = m->p;
+  if (!p.useGMRedi || !p.GM_AdvForm) return false;
+  if (p.tempStepping && scheme_multi_dim(p, p.tempAdvection, p.tempAdvScheme)) return true;
+  if (p.saltStepping && scheme_multi_dim(p, p.saltAdvection, p.saltAdvScheme)) return true;
+  for (const auto &t : m->ptr)
+    if (scheme_multi_dim(p, 1, t.advScheme)) return true;
+  return false;
+}
+// what both builders derive from the model: the scheme's fields (a.advection is set) and the
+// flow the multi-dimensional passes advect by
+// res: takes_res_flow(m), evaluated once by the caller
+static void tracer_args_common(const mgcm_model *m, int scheme, bool res, TracerArgs &a) {
+  a.dT = m->p.deltaTtracer;
+  a.multiDim = scheme_multi_dim(m->p, a.advection, scheme);
+  a.useAB = scheme_is_ab(scheme);
+  a.limiter = scheme == 33;   // DST3 (30) without, DST3FL (33) with the flux limiter
+  a.scheme = scheme;
+  a.advU = res ? m->f.uRes : m->f.uVel;
+  a.advV = res ? m->f.vRes : m->f.vVel;
+  a.advW = res ? m->f.wRes : m->f.wVel;
+}
+
 static TracerArgs tracer_args(const mgcm_model *m, bool salt) {
   const Params &p = m->p;
   TracerArgs a{};
@@ -1734,17 +1710,12 @@ static TracerArgs tracer_args(const mgcm_model *m, bool salt) {
   a.sfc = salt ? m->f.surfaceForcingS : m->f.surfaceForcingT;
   a.diffKh = salt ? p.diffKhS : p.diffKhT;
   a.diffKr = salt ? p.diffKrS : p.diffKrT;
-  a.dT = p.deltaTtracer;
   a.advection = salt ? p.saltAdvection : p.tempAdvection;
   a.forcing = salt ? p.saltForcing : p.tempForcing;
-  // gad_init_fixed.F:126-162: multi-dim advection for the schemes that are not
-  // Adams-Bashforth ones; AB (2 or 3) on the tendency for C2, U3 and C4
-  const bool abScheme = scheme == 2 || scheme == 3 || scheme == 4;
-  a.multiDim = p.multiDimAdvection && a.advection && !abScheme;
-  a.useAB = abScheme;
-  a.limiter = scheme == 33;   // DST3 (30) without, DST3FL (33) with the flux limiter
-  a.scheme = scheme;
   a.gNm2 = salt ? m->f.gsNm2 : m->f.gtNm2;
+  a.gm = p.useGMRedi;
+  a.adv1 = m->f.advScr1; a.adv2 = m->f.advScr2; a.gAdv = m->f.gAdv;
+  tracer_args_common(m, scheme, takes_res_flow(m), a);
   return a;
 }
 
@@ -1752,7 +1723,7 @@ static TracerArgs tracer_args(const mgcm_model *m, bool salt) {
 // sequence with the tracer's own parameters (PTRACERS_advScheme, _diffKh, _diffKr,
 // _useGMRedi), its own buffers and scratch, and the forcing restated from the reference's
 // experiment code (common.h TracerArgs).  flip: the parity the arguments are for.
-static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip) {
+static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip, bool res) {
   const Params &p = m->p;
   const mgcm_model::PTracer &t = m->ptr[i];
   TracerArgs a{};
@@ -1764,20 +1735,15 @@ static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip) {
   a.sfc = nullptr;   // surfaceForcingPTr = 0 (PTRACERS_EvPrRn unset) unless the relaxation below
   a.diffKh = t.diffKh;
   a.diffKr = t.diffKr;
-  a.dT = p.deltaTtracer;
   a.advection = 1;
   a.forcing = 0;
-  const bool abScheme = t.advScheme == 2 || t.advScheme == 3 || t.advScheme == 4;
-  a.multiDim = p.multiDimAdvection && !abScheme;
-  a.useAB = abScheme;
-  a.limiter = t.advScheme == 33;
-  a.scheme = t.advScheme;
   a.gNm2 = nullptr;   // (ADAMS_BASHFORTH3 is refused with passive tracers)
   a.relaxRate = t.surfRelaxTau != 0.0 ? 1.0 / t.surfRelaxTau : 0.0;
   a.relaxVal = t.surfRelaxVal;
   a.src = t.interiorSource;
   a.gm = p.useGMRedi && t.useGMRedi != 0;
   a.adv1 = t.adv1; a.adv2 = t.adv2; a.gAdv = t.gAdv;
+  tracer_args_common(m, t.advScheme, res, a);
   return a;
 }
 // MGCM_PTR_BATCH=1: the batched kernels wherever they apply (kernels_ptracers.hip ptr_batch_ok:
@@ -1804,13 +1770,19 @@ static bool ptr_batched(const mgcm_model *m) {
   return ptr_batch_ok(m->d, m->p, m->ptrNMd > 0);
 }
 // The batched kernels' device tables, one per parity: uploaded by mgcm_init and, after a
-// parameter change, by the next entry point that steps (never inside a graph capture)
+// parameter change, by the next entry point that steps (never inside a graph capture).  An entry
+// depends on the tracer's own parameters, on deltaTtracer, on what takes_res_flow reads --
+// useGMRedi, GM_AdvForm, multiDimAdvection, temp / saltStepping, temp / saltAdvection,
+// temp / saltAdvScheme and every tracer's advScheme -- and on device pointers fixed at
+// allocation.  All of these change through mgcm_set_param, mgcm_ptracer_param or
+// mgcm_ptracers_alloc, which mark the tables dirty (as mgcm_init does).
 static int ptr_tables_sync(mgcm_model *m) {
   const int n = (int)m->ptr.size();
   if (!n || !m->ptrTabDirty) return 0;
   std::vector<TracerArgs> tab(2 * (size_t)n);
+  const bool res = takes_res_flow(m);
   for (int q = 0; q < 2; q++)
-    for (int i = 0; i < n; i++) tab[(size_t)q * n + i] = tracer_args_ptr(m, i, q);
+    for (int i = 0; i < n; i++) tab[(size_t)q * n + i] = tracer_args_ptr(m, i, q, res);
   // launch order: the GM/Redi tracers first (their own kernel), and in each kind the longest
   // bodies first -- U3 / C4 inside GAD_CALC_RHS, then C2, then the multi-dimensional tracers
   // (their advection ran in the passes)
@@ -1841,7 +1813,6 @@ static int ptr_tables_sync(mgcm_model *m) {
 // swap together (CYCLE_TRACER)
 static int ptracers_on(mgcm_model *m, hipStream_t st) {
   const int n = (int)m->ptr.size();
-  const bool resFlow = m->gmResFlow != 0;   // (res_flow_on ran ahead: every multi-dimensional tracer takes it)
   m->ptrRoute = 0;
   m->ptrLaunches = 0;
   if (!n) return 0;
@@ -1849,15 +1820,12 @@ static int ptracers_on(mgcm_model *m, hipStream_t st) {
   if (ptr_batched(m)) {
     m->ptrRoute = 2;
     TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
-                                        m->ptrNGM, m->d_ctr, st, &m->ptrLaunches, resFlow));
+                                        m->ptrNGM, m->d_ctr, st, &m->ptrLaunches));
   } else {
     m->ptrRoute = 1;
-    for (int i = 0; i < n; i++) {
-      const TracerArgs a = tracer_args_ptr(m, i, m->ptrFlip);
-      Params pp = m->p;
-      pp.useGMRedi = a.gm;
-      TIMED(K_TEMP, launch_tracer_step(m->d, pp, ptr_fields(m->f, a), a, m->d_ctr, st, true, &m->ptrLaunches, resFlow));
-    }
+    const bool res = takes_res_flow(m);
+    for (int i = 0; i < n; i++)
+      TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, tracer_args_ptr(m, i, m->ptrFlip, res), m->d_ctr, st, true, &m->ptrLaunches));
   }
   for (int i0 = 0; i0 < n; i0 += MG_XMAX) {
     XFields x{};
@@ -1868,14 +1836,17 @@ static int ptracers_on(mgcm_model *m, hipStream_t st) {
   return 0;
 }
 
-// GMREDI_RESIDUAL_FLOW (thermodynamics.F:252-270) at the head of THERMODYNAMICS, where the plan
-// has it (StepPlan::resFlow); defined with the plan
-static int res_flow_on(mgcm_model *m, hipStream_t st);
+// GMREDI_RESIDUAL_FLOW (thermodynamics.F:252-270) at the head of THERMODYNAMICS, where the model
+// takes it (StepPlan::resFlow); gmResFlow: what mgcm_get_param reports, nothing here reads it
+static int res_flow_on(mgcm_model *m, hipStream_t st) {
+  m->gmResFlow = takes_res_flow(m) ? 1 : 0;
+  if (m->gmResFlow) TIMED(K_TEMP, launch_gm_residual_flow(m->d, m->p, m->f, st));
+  return 0;
+}
 
 // TEMP_INTEGRATE / SALT_INTEGRATE (and PTRACERS_INTEGRATE) on stream `st` (the ping-pong swaps are host-side)
 static int tracers_on(mgcm_model *m, hipStream_t st) {
   if (res_flow_on(m, st)) return -1;
-  const bool resFlow = m->gmResFlow != 0;
   const TracerArgs aT = tracer_args(m, false), aS = tracer_args(m, true);
   if (tracer_hpair_ok(m->d, m->p, aT, aS)) {   // small grids: both tracers per launch
     TIMED(K_TEMP, launch_tracer_hpair(m->d, m->p, m->f, aT, aS, m->d_ctr, st));
@@ -1884,11 +1855,11 @@ static int tracers_on(mgcm_model *m, hipStream_t st) {
     return ptracers_on(m, st);
   }
   if (m->p.tempStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aT, m->d_ctr, st, true, nullptr, resFlow));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aT, m->d_ctr, st));
     std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new theta is the other buffer
   }
   if (m->p.saltStepping) {
-    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aS, m->d_ctr, st, true, nullptr, resFlow));
+    TIMED(K_TEMP, launch_tracer_step(m->d, m->p, m->f, aS, m->d_ctr, st));
     std::swap(m->f.salt, m->f.saltNext);
   }
   return ptracers_on(m, st);
@@ -2189,7 +2160,8 @@ struct StepPlan {
   bool pipeOk, phiPipeOk, pipe, hoist, valid, phiPipe, phiNext, empNext;
   // GMREDI_RESIDUAL_FLOW as a launch of its own (k_gm_residual_flow -> uRes, vRes, wRes): under
   // GM_AdvForm when a stepped tracer -- theta, salt or a passive one -- takes GAD_ADVECTION's
-  // multi-dimensional passes, which then advect by those fields.  It reads the step's whole
+  // multi-dimensional passes (takes_res_flow; their TracerArgs then name those fields as the
+  // flow to advect by).  It reads the step's whole
   // tensor (Psi at i+1, j+1) and u, v, w with the halos THERMODYNAMICS sees, so it opens
   // THERMODYNAMICS wherever that runs (tracers_on, on the tracers' stream: after the tensor's
   // grid, and on the staggered cube after DO_STAGGER_FIELDS_EXCHANGES); resFlowFold: where the
@@ -2199,8 +2171,6 @@ struct StepPlan {
   // most, and the residual flow reads it over the whole slab
   bool resFlow, resFlowFold;
 };
-static TracerArgs tracer_args(const mgcm_model *m, bool salt);
-static TracerArgs tracer_args_ptr(const mgcm_model *m, int i, int flip);
 static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const Params &p = m->p;
   const Dims &d = m->d;
@@ -2219,11 +2189,7 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const bool ringSep = mom_ring_separable(d, p);
   pl.ringLate = pl.forkLate && ringSep && mg_fuse_on(MG_FUSE_RING);
   pl.ringAside = pl.thermoLate && pl.ringLate;
-  pl.resFlow = false;
-  if (p.useGMRedi && p.GM_AdvForm && pl.tracers) {
-    pl.resFlow = (p.tempStepping && tracer_args(m, false).multiDim) || (p.saltStepping && tracer_args(m, true).multiDim);
-    for (int i = 0; i < (int)m->ptr.size() && !pl.resFlow; i++) pl.resFlow = tracer_args_ptr(m, i, 0).multiDim != 0;
-  }
+  pl.resFlow = takes_res_flow(m);
   pl.dtFused = pl.forkable && pl.rstar && dyn_thermo_fusable(d, p, tracer_args(m, false), tracer_args(m, true));
   // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
   const bool gmFold = pl.dtFused && dyn_thermo_takes_gm(p);
@@ -2263,12 +2229,6 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
 static int step_layout_bits(const StepPlan &pl) {
   return (pl.dtFused ? 1 : 0) | (pl.forkable && !pl.dtFused ? 4 : 0) | (pl.forkable && pl.forkLate ? 8 : 0) |
          (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0);
-}
-
-static int res_flow_on(mgcm_model *m, hipStream_t st) {
-  m->gmResFlow = plan_step(m, STEP_PLAIN).resFlow ? 1 : 0;
-  if (m->gmResFlow) TIMED(K_TEMP, launch_gm_residual_flow(m->d, m->p, m->f, st));
-  return 0;
 }
 
 // THERMODYNAMICS onto the second stream (after the model stream's work so far), evJoin behind

@@ -13,6 +13,8 @@ multi-dimensional pass of theta, salt and the passive tracers in place of the Eu
      gmResFlow reads 1; with scheme 2 it reads 0 and the step issues what it issues in skew form;
   5  passive tracers on schemes 33, 30 and 2 on both routes (MGCM_PTR_BATCH = 0 / 1) against the
      oracle's salt stand-in (test_gpu_ptracers.py), on cs32x15 and tutorial_global_oce_latlon;
+     and a tracer's own useGMRedi = 0 on schemes 2 and 3 (the Eulerian velocity, no GM/Redi flux)
+     beside a scheme-2 tracer that keeps GM/Redi, from the same field;
   6  forward_step(6) against six forward_step(1), and with the pipelined-step bits off;
   7  two tile-sharded processes against one.
 
@@ -182,6 +184,11 @@ def test_cs32x15_the_two_forms_differ_and_scheme_2_is_left_alone():
 # ---- 5: passive tracers, both routes -------------------------------------------------------------
 PTR_SPECS = (dict(advScheme=33, diffKr=3e-5, useGMRedi=1), dict(advScheme=30, diffKr=1e-5, useGMRedi=1),
              dict(advScheme=2, diffKh=300.0, useGMRedi=1))
+# the tracer's own switch (PTRACERS_useGMRedi) off under GM_AdvForm: tracer 3 starts from tracer
+# 1's field (same_as, read by the tests only) and differs from it in the switch alone
+PTR_GM_OFF_SPECS = (dict(advScheme=2, diffKh=300.0, useGMRedi=0), dict(advScheme=3, diffKr=1e-5, useGMRedi=0),
+                    dict(advScheme=2, diffKh=300.0, useGMRedi=1, same_as=1))
+SPEC_SETS = {"gm_on": PTR_SPECS, "gm_off": PTR_GM_OFF_SPECS}
 
 
 def _latlon_cfg(**kw):
@@ -195,11 +202,15 @@ def _cs32_ptr_cfg():
 
 
 @functools.lru_cache(maxsize=None)
-def _standin_reference(which):
+def _standin_reference(which, specs="gm_on"):
     """test_gpu_ptracers.py's _latlon_reference under GM_AdvForm, for either experiment: oracle
     steps, DO_OCEANIC_PHYS with the true salt, then per tracer THERMODYNAMICS with salt := X,
-    saltForcing = 0 and the tracer's scheme and diffusivities.  Computed once and shared by the
-    two routes (do not modify)."""
+    saltForcing = 0 and the tracer's scheme and diffusivities.  A tracer with useGMRedi = 0:
+    GM/Redi off in the oracle for its THERMODYNAMICS call only (DO_OCEANIC_PHYS and the tensor ran
+    with it on), as test_gpu_ptracers_sweep.py's stand-in does.  A spec's same_as names the tracer
+    whose initial field it shares.  Computed once per (experiment, list) and shared by the two routes (do not
+    modify)."""
+    specs = SPEC_SETS[specs]
     from oracle.harness import cs32x15_oracle, latlon_oracle
     if which == "latlon":
         o, g = latlon_oracle()
@@ -218,16 +229,20 @@ def _standin_reference(which):
     assert np.abs(np.array(o.arr("GM_PsiX"))).max() > 0.0
     keep = {n: np.array(o.arr(n)) for n in ("theta", "salt", "gtNm1", "gsNm1", "surfaceForcingS")}
     rng = np.random.default_rng(20261021)
-    xs = [_wet_random(g, rng) for _ in PTR_SPECS]
+    xs = [_wet_random(g, rng) for _ in specs]
+    for no, sp in enumerate(specs):
+        if "same_as" in sp:
+            xs[no] = xs[sp["same_as"] - 1]
     out = []
-    for sp, x in zip(PTR_SPECS, xs):
+    for sp, x in zip(specs, xs):
         for n, v in keep.items():
             o.arr(n)[:] = v
         o.arr("salt")[:] = x
         s = sp["advScheme"]
         o.set(saltAdvScheme=s, saltVertAdvScheme=s, diffKhS=sp.get("diffKh", 0.0), diffKrS=sp.get("diffKr", 0.0),
-              saltForcing=0, multiDimAdvection=1)
+              saltForcing=0, multiDimAdvection=1, useGMRedi=int(sp["useGMRedi"]))
         o.L.oracle_thermodynamics(o.h)
+        o.set(useGMRedi=1)
         out.append((np.array(o.arr("salt")), np.array(o.arr("gsNm1"))))
     for a in list(state.values()) + xs + [b for pair in out for b in pair]:
         a.setflags(write=False)
@@ -262,6 +277,49 @@ def test_ptracers_one_thermodynamics_bitexact(which, batch, monkeypatch):
         if not np.array_equal(m.get("gpTrNm1_03")[inner], ref[2][1][inner]):
             bad.append("gpTrNm1_03")
         assert not bad, bad
+        for n in ("theta", "salt", "gtNm1", "gsNm1"):
+            assert np.array_equal(m.get(n), plain.get(n)), n
+    finally:
+        m.close()
+        plain.close()
+
+
+@pytest.mark.parametrize("batch", [0, 1])
+def test_ptracers_own_gm_switch_off_bitexact(batch, monkeypatch):
+    """One THERMODYNAMICS call on tutorial_global_oce_latlon under GM_AdvForm with PTR_GM_OFF_SPECS.
+    A tracer whose useGMRedi is 0 is stepped as the oracle's salt with GM/Redi off for that call:
+    by the Eulerian velocity, without the GM/Redi fluxes, Kwz left out of its implicit solve
+    (DESIGN.md section 7 names the scheme-2 case as a known deviation from the reference).
+    Tracers 1 and 3 start from the same field and differ in the switch alone."""
+    from mitgcm_amd import configs
+    monkeypatch.setenv("MGCM_PTR_BATCH", str(batch))
+    g, state, myIter, gs0, xs, ref = _standin_reference("latlon", "gm_off")
+    m = configs.make_model(_latlon_cfg, ptracers=[dict({k: v for k, v in sp.items() if k != "same_as"}, init=x)
+                                                   for sp, x in zip(PTR_GM_OFF_SPECS, xs)])
+    plain = configs.make_model(_latlon_cfg)
+    try:
+        for x in (m, plain):
+            _put_state(x, state, myIter)
+        for no in (1, 2, 3):   # (schemes 2 and 3: every tracer has an AB history)
+            m.put("gpTrNm1_%02d" % no, gs0)
+        m.thermodynamics()
+        plain.thermodynamics()
+        assert not m.gm_res_flow()   # (no multi-dimensional tracer)
+        assert m.ptracers_route()["route"] == ("batched" if batch else "functional"), m.ptracers_route()
+        inner = _inner(g)
+        bad = []
+        for no, (salt, gs) in enumerate(ref, 1):
+            dev, hist = m.get("pTracer%02d" % no), m.get("gpTrNm1_%02d" % no)
+            print("pTracer%02d max |device - oracle| on the interior:" % no, float(np.abs(dev - salt)[inner].max()),
+                  "gpTrNm1:", float(np.abs(hist - gs)[inner].max()))
+            if not np.array_equal(dev[inner], salt[inner]):
+                bad.append((no, float(np.abs(dev - salt)[inner].max())))
+            if not np.array_equal(hist[inner], gs[inner]):
+                bad.append(("gpTrNm1_%02d" % no, float(np.abs(hist - gs)[inner].max())))
+            assert not np.array_equal(dev[inner], xs[no - 1][inner])
+        assert not bad, bad
+        assert np.array_equal(xs[0], xs[2])
+        assert not np.array_equal(m.get("pTracer01")[inner], m.get("pTracer03")[inner])   # the switch is read
         for n in ("theta", "salt", "gtNm1", "gsNm1"):
             assert np.array_equal(m.get(n), plain.get(n)), n
     finally:
