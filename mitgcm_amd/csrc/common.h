@@ -264,7 +264,7 @@ inline size_t mg_colf_lds(int Nr, int nc, int nArr) { return (size_t)nArr * Nr *
   } while (0)
 inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + nc - 1) / nc); }
 // Launch fusions of FORWARD_STEP, each switchable for A/B runs: MGCM_STEP_FUSE = bit mask of
-// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
+// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP | SPEC): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
 // MG_FUSE_PHI CALC_PHI_HYD + del2uv in one grid, MG_FUSE_END CALC_R_STAR + the blocking
 // exchanges in one grid, MG_FUSE_TREX the
 // tracers' halo exchange on their own stream beside the pressure solve (late join only;
@@ -282,6 +282,9 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 // MG_PIPE_MIN_STEPS steps or more; one_step's StepMode, model.hip), MG_FUSE_PHIP (with
 // MG_FUSE_PIPE) the next step's CALC_PHI_HYD and del2uv in this step's CALC_R_STAR + exchange grid
 // (k_rstar_exch_phi, kernels_step.hip): the pipelined step then starts at the momentum launch.
+// MG_FUSE_SPEC no launch fusion but a choice of instantiation: the fold's second and third grid
+// (k_dt_l2, k_dt_l3) compiled for global_ocean.90x40x15's option set (OptsGO90 below) where the
+// model's options are that set; bit-identical, every other configuration runs the generic ones.
 // The step's fusions are decided in one place, model.hip's plan_step; the kernel files' own
 // *_fusable / *_ok predicates, which it calls, read their bits here too.
 // Four bits are retired (round 10): each was off by default, bit-identical and measured slower
@@ -300,15 +303,15 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 //       UPDATE_R_STAR rewrites it: on config 2 the fold into DYNAMICS' launches stays faster,
 //       0.2885 against 0.307 ms/step (profiles/r04/tcg/) -- the tracers' launches beside
 //       DYNAMICS cost more than the 190 us single-CU solve they could hide behind.
-// The twelve others keep their values (tests and tools pass numeric masks).
+// The thirteen others keep their values (tests and tools pass numeric masks).
 enum { MG_FUSE_SFP = 1, MG_FUSE_PHI = 4, MG_FUSE_END = 8, MG_FUSE_TREX = 64, MG_FUSE_DT = 128, MG_FUSE_ETAX = 256,
        MG_FUSE_OPE = 1024, MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384,
-       MG_FUSE_PHIP = 32768 };
+       MG_FUSE_PHIP = 32768, MG_FUSE_SPEC = 65536 };
 inline int mg_fuse_mask() {
   // read per call (tests switch it per model)
   return getenv("MGCM_STEP_FUSE") ? atoi(getenv("MGCM_STEP_FUSE"))
                                   : MG_FUSE_SFP | MG_FUSE_PHI | MG_FUSE_END | MG_FUSE_DT | MG_FUSE_ETAX | MG_FUSE_OPE |
-                                        MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE | MG_FUSE_PHIP;
+                                        MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE | MG_FUSE_PHIP | MG_FUSE_SPEC;
 }
 inline bool mg_fuse_on(int bit) { return (mg_fuse_mask() & bit) != 0; }
 // the lowest retired bit the mask sets (0: none), and what it selected
@@ -329,6 +332,70 @@ inline bool mg_hfuse(int bit, long nx, long ny, long nT, long Nr) {
 }
 inline unsigned mg_plane_blocks(int ni, int nj, int nz) {
   return (unsigned)(((ni) * (nj) + MG_PLANE_THREADS - 1) / MG_PLANE_THREADS * (nz));
+}
+
+// The option set of the step's bodies as a type.  The bodies ask their questions of Params
+// through one of these (template parameter O, O::rstar(p), ...) instead of reading the fields:
+//   OptsRun   answers from Params, with the expressions the bodies always tested: the generic
+//             instantiations (same occupancy; their registers moved by one or two);
+//   OptsGO90  answers with global_ocean.90x40x15's values as constants, so the branches of the
+//             options that configuration never takes (and the full vmcnt waits that end each of
+//             them) are not compiled at all.  Only which code is compiled changes: every
+//             expression that remains, and its operand order, is the generic one.
+//             One question stays a run-time test on purpose, momAdvection: with it folded the
+//             advective stage's loads (some 40 doubles) merge into the block of the viscous
+//             stage's and the momentum halves need 151-156 VGPRs, 3 waves per SIMD -- k_dt_l2's
+//             1008 workgroups then no longer fit the chip in one round.  Behind that one
+//             uniform branch they need 104 (profiles/r14/step_spec/resource_usage.md).
+// MG_OPT_LIST is the one list of the questions: X(name, run-time expression of p, pinned value).
+// opts_match(p) below compares the two answer by answer; model.hip's plan_step launches the
+// pinned instantiations only where it holds (StepPlan::spec, MG_FUSE_SPEC).
+#define MG_OPT_LIST(X)                                                                              \
+  X(momAdvection, p.momAdvection != 0, p.momAdvection != 0)   /* kept a branch, see OptsGO90 */     \
+  X(momViscosity, p.momViscosity != 0, true)                                                        \
+  X(momForcing, p.momForcing != 0, true)                                                            \
+  X(rstar, p.nonlinFreeSurf > 0 && p.select_rStar > 0, true)   /* r* coordinate */                 \
+  X(rstarOn, p.select_rStar > 0, true)                                                              \
+  X(rstar2, p.select_rStar >= 2, true)                                                              \
+  X(nlfs0, p.nonlinFreeSurf > 0, true)                                                              \
+  X(nlfs2, p.nonlinFreeSurf > 1, true)                                                              \
+  X(nlfs4, p.nonlinFreeSurf >= 4, true)                                                             \
+  X(biharmonic, p.viscA4D != 0.0 || p.viscA4Z != 0.0, true)                                         \
+  X(noSlipSides, p.no_slip_sides != 0, true)                                                        \
+  X(noSlipBottom, p.no_slip_bottom != 0, true)                                                      \
+  X(nhmTerms, p.useNHMTerms != 0, true)                                                             \
+  X(metricSphere, p.metricSphere != 0, true)                                                        \
+  X(coriolis, p.useCoriolis != 0, true)                                                             \
+  X(cori3d, p.select3dCoriScheme >= 1, true)                                                        \
+  X(cdScheme, p.useCDscheme != 0, true)                                                             \
+  X(dissipInAB, p.momDissip_In_AB != 0, true)                                                       \
+  X(forcingOutAB, p.momForcingOutAB == 1, false)                                                    \
+  X(implicitViscosity, p.implicitViscosity != 0, false)                                             \
+  X(gmAdvForm, p.GM_AdvForm != 0, false)                                                            \
+  X(gmExtraDiag, p.GM_ExtraDiag != 0, false)                                                        \
+  X(implicitDiffusion, p.implicitDiffusion != 0, true)                                              \
+  X(tracForcingOutAB, p.tracForcingOutAB != 0, false)
+struct OptsRun {
+  static constexpr bool pinned = false;
+#define MG_OPT_RUN(name, expr, pin) \
+  __host__ __device__ __forceinline__ static bool name(const Params &p) { return (expr); }
+  MG_OPT_LIST(MG_OPT_RUN)
+#undef MG_OPT_RUN
+};
+struct OptsGO90 {
+  static constexpr bool pinned = true;
+#define MG_OPT_PIN(name, expr, pin) \
+  __host__ __device__ __forceinline__ static constexpr bool name(const Params &p) { (void)p; return (pin); }
+  MG_OPT_LIST(MG_OPT_PIN)
+#undef MG_OPT_PIN
+};
+// whether a model's parameters are the pinned set (every question of MG_OPT_LIST answered alike)
+inline bool opts_match(const Params &p) {
+#define MG_OPT_EQ(name, expr, pin) \
+  if (OptsRun::name(p) != OptsGO90::name(p)) return false;
+  MG_OPT_LIST(MG_OPT_EQ)
+#undef MG_OPT_EQ
+  return true;
 }
 
 // The serial end of SOLVE_FOR_PRESSURE's right-hand side for one column (k_sfp_rhs and the

@@ -35,8 +35,9 @@ __device__ __forceinline__ double hfacz(const Dims &d, const Fields &f, int i, i
 
 // h0FacZ (mom_fluxform.F:290-307): from the rest-state h0FacW/S under the non-linear
 // free surface with no-slip walls, else hFacZ
+template <class O = OptsRun>
 __device__ __forceinline__ double h0facz(const Dims &d, const Params &p, const Fields &f, int i, int j, int k, int t) {
-  if (!(p.momViscosity && p.no_slip_sides && p.nonlinFreeSurf > 0)) return hfacz(d, f, i, j, k, t);
+  if (!(O::momViscosity(p) && O::noSlipSides(p) && O::nlfs0(p))) return hfacz(d, f, i, j, k, t);
   if (i < 2 - d.OLx || j < 2 - d.OLy) return 0.0;
   return fmin(fmin(f.h0FacW[MG_I3(d, i, j, k, t)], f.h0FacW[MG_I3(d, i, j - 1, k, t)]),
               fmin(f.h0FacS[MG_I3(d, i, j, k, t)], f.h0FacS[MG_I3(d, i - 1, j, k, t)]));
@@ -821,7 +822,7 @@ __device__ __forceinline__ void vecinv_tend(const A &a, const Dims &d, const P &
 // viscous ones, whose sum guDiss / gvDiss it takes from *sD after the workgroup barrier; 2 the
 // viscous terms only, stored to *sD before that barrier (the other role's wave of the same
 // points).  valid = false: no arithmetic, only the barrier (PART 1 / 2 reach it on every lane).
-template <bool VI, int COMP, int PART = 0>
+template <bool VI, int COMP, int PART = 0, class O = OptsRun>
 __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, int i,
                                              int j, int z, bool valid, double *sD) {
   static_assert(PART == 0 || (!VI && COMP != 0), "the viscous split is per component, flux form");
@@ -838,10 +839,10 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
   const double mass2rUnit = 1.0 / p.rhoConst;
   const double uDudxFac = p.afFacMom, vDudyFac = p.afFacMom, rVelDudrFac = p.afFacMom;
   const double AhDudxFac = p.vfFacMom, AhDudyFac = p.vfFacMom;
-  const double ArDudrFac = p.implicitViscosity ? 0.0 : p.vfFacMom;
+  const double ArDudrFac = O::implicitViscosity(p) ? 0.0 : p.vfFacMom;
   const double fuFac = p.cfFacMom, fvFac = p.cfFacMom;
   const long q2 = MG_I2(d, i, j, t);
-  const bool rstar = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
+  const bool rstar = O::rstar(p);
 
 #define U(ii, jj, kk) AR3(uVel, MG_I3(d, ii, jj, kk, t))
 #define V(ii, jj, kk) AR3(vVel, MG_I3(d, ii, jj, kk, t))
@@ -889,14 +890,14 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
     if (valid && inner && PART != 2) {
       // CALC_GRAD_PHI_HYD (calc_grad_phi_hyd.F:152-171), phi0surf = 0
       // r* (select_rStar >= 2, nonlinFreeSurf >= 4): varLoc = phiHydC*rStarFacC + phi0surf (:30-47)
-      const bool rsc = rstar && p.select_rStar >= 2 && p.nonlinFreeSurf >= 4;
+      const bool rsc = rstar && O::rstar2(p) && O::nlfs4(p);
       auto varLoc = [&](int ii, int jj) {
         return rsc ? G3(phiHydC, ii, jj, k) * G2(rStarFacC, ii, jj) + 0.0 : G3(phiHydC, ii, jj, k) + 0.0;
       };
       const double vl = varLoc(i, j);
       if (i >= 1) dPhiHydX = G2(recip_dxC, i, j) * (vl - varLoc(i - 1, j));
       if (j >= 1) dPhiHydY = G2(recip_dyC, i, j) * (vl - varLoc(i, j - 1));
-      if (rstar && p.select_rStar >= 2) {
+      if (rstar && O::rstar2(p)) {
         // calc_grad_phi_hyd.F:173-214 (fluidIsWater, z-coords, generalForm = F)
         const double factorP = p.gravity * (1.0 / p.rhoConst) * 0.5, rCk = f.rC[k - 1];
         auto vl2 = [&](int ii, int jj) { return G2(etaH, ii, jj) * (1.0 + rCk * G2(recip_Rcol, ii, jj)); };
@@ -914,7 +915,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
         vecinv_tend(VIGlobal{d, p, f, k, t}, d, p, f, i, j, k, t, gU, gV, guDiss, gvDiss);
       } else {
       // ---------------- advection (mom_u_adv_uu/vu/wu.F, mom_v_adv_uv/vv/wv.F)
-      if (PART != 2 && p.momAdvection) {
+      if (PART != 2 && O::momAdvection(p)) {
         const double fVerUkm = fverU(k), fVerUkp = fverU(k + 1);
         const double fVerVkm = fverV(k), fVerVkp = fverV(k + 1);
         // uTrans / vTrans (mom_fluxform.F:287-327)
@@ -940,10 +941,10 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
 #undef VTR
       }
       // ---------------- viscosity (mom_u/v_x/y/rviscflux.F, sidedrag, botdrag)
-      if (PART != 1 && p.momViscosity) {
+      if (PART != 1 && O::momViscosity(p)) {
         // U: xviscflux at i and i-1, yviscflux at j+1 and j
         // v4F = del2u / del2v from k_del2uv (0 without biharmonic viscosity)
-        const bool bh = p.viscA4D != 0.0 || p.viscA4Z != 0.0;
+        const bool bh = O::biharmonic(p);
         auto D2U = [&](int ii, int jj) { return bh ? G3(del2u, ii, jj, k) : 0.0; };
         auto D2V = [&](int ii, int jj) { return bh ? G3(del2v, ii, jj, k) : 0.0; };
         const double d2u = D2U(i, j), d2v = D2V(i, j);
@@ -968,10 +969,10 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
                   G3(maskW, i, j, k + 1) * G3(maskW, i, j, k);
         guDiss = -rhFacW * recip_drF * G2(recip_rAw, i, j) *
                  ((fZi - fZm) * AhDudxFac + (fMp - fMi) * AhDudyFac + (fVrDw - fVrUp) * p.rkSign * ArDudrFac);
-        if (p.no_slip_sides) {
+        if (O::noSlipSides(p)) {
           // MOM_U_SIDEDRAG with NONLIN_FRSURF: h0FacW - h0FacZ (h0Fac = hFac at rest)
-          const double hS = G3(h0FacW, i, j, k) - h0facz(d, p, f, i, j, k, t);
-          const double hN = G3(h0FacW, i, j, k) - h0facz(d, p, f, i, j + 1, k, t);
+          const double hS = G3(h0FacW, i, j, k) - h0facz<O>(d, p, f, i, j, k, t);
+          const double hN = G3(h0FacW, i, j, k) - h0facz<O>(d, p, f, i, j + 1, k, t);
           const double u0 = U(i, j, k);
           const double vF = -rhFacW * recip_drF * G2(recip_rAw, i, j) *
                             (hS * G2(dxV, i, j) * G2(recip_dyU, i, j) * (p.viscAhZ * u0 - p.viscA4Z * d2u) +
@@ -979,7 +980,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
                             drF * p.sideDragFactor;
           guDiss = guDiss + vF;
         }
-        if (p.no_slip_bottom) {
+        if (O::noSlipBottom(p)) {
           const int kDn = (k + 1 < Nr) ? k + 1 : Nr, kLowF = k + 1;
           const double recDrC = (k == Nr) ? recip_drF : f.recip_drC[kLowF - 1];
           double cD = 0.0 * 1.0;
@@ -1009,9 +1010,9 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
                   G3(maskS, i, j, k + 1) * G3(maskS, i, j, k);
         gvDiss = -rhFacS * recip_drF * G2(recip_rAs, i, j) *
                  ((gZp - gZi) * AhDudxFac + (gMi - gMm) * AhDudyFac + (gVrDw - gVrUp) * p.rkSign * ArDudrFac);
-        if (p.no_slip_sides) {
-          const double hW = G3(h0FacS, i, j, k) - h0facz(d, p, f, i, j, k, t);
-          const double hE = G3(h0FacS, i, j, k) - h0facz(d, p, f, i + 1, j, k, t);
+        if (O::noSlipSides(p)) {
+          const double hW = G3(h0FacS, i, j, k) - h0facz<O>(d, p, f, i, j, k, t);
+          const double hE = G3(h0FacS, i, j, k) - h0facz<O>(d, p, f, i + 1, j, k, t);
           const double v0 = V(i, j, k);
           const double vF = -rhFacS * recip_drF * G2(recip_rAs, i, j) *
                             (hW * G2(dyU, i, j) * G2(recip_dxV, i, j) * (p.viscAhZ * v0 - p.viscA4Z * d2v) +
@@ -1019,7 +1020,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
                             drF * p.sideDragFactor;
           gvDiss = gvDiss + vF;
         }
-        if (p.no_slip_bottom) {
+        if (O::noSlipBottom(p)) {
           const int kDn = (k + 1 < Nr) ? k + 1 : Nr, kLowF = k + 1;
           const double recDrC = (k == Nr) ? recip_drF : f.recip_drC[kLowF - 1];
           double cD = 0.0 * 1.0;
@@ -1029,7 +1030,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
         }
       }
       // ---------------- spherical metric terms (mom_u/v_metric_sphere.F, mom_fluxform.F:714-721, 973-980)
-      if (PART != 2 && p.useNHMTerms) {
+      if (PART != 2 && O::nhmTerms(p)) {
         // MOM_U/V_METRIC_NH (pkg/mom_common/mom_u_metric_nh.F:56-68, mom_v_metric_nh.F), mtNHFac = 1
         const int kp1 = k + 1 < Nr ? k + 1 : Nr;
         const double ov = (k == Nr) ? 0.0 : 1.0;
@@ -1038,7 +1039,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
         gV = gV + 1.0 * (V(i, j, k) * p.recip_rSphere * 0.25 *
                          ((W(i, j - 1, kp1) + W(i, j, kp1)) * ov + (W(i, j - 1, k) + W(i, j, k))) * p.gravitySign);
       }
-      if (PART != 2 && p.metricSphere) {
+      if (PART != 2 && O::metricSphere(p)) {
         const double mTu = U(i, j, k) * p.recip_rSphere * 0.25 *
                            (V(i, j, k) + V(i - 1, j, k) + V(i, j + 1, k) + V(i - 1, j + 1, k)) * G2(tanPhiAtU, i, j);
         gU = gU + p.mtFacMom * mTu;
@@ -1048,7 +1049,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
       }
       // ---------------- Coriolis (mom_u_coriolis.F, mom_v_coriolis.F); with the CD scheme
       // it is applied in TIMESTEP instead (mom_fluxform.F:995, k_cd_scheme)
-      if (PART != 2 && p.useCoriolis && !p.useCDscheme) {
+      if (PART != 2 && O::coriolis(p) && !O::cdScheme(p)) {
         const int sc = p.selectCoriScheme;
         double c;
         if (sc >= 2)
@@ -1070,7 +1071,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
           c = c * 4.0 / fmax(1.0, G3(maskW, i, j, k) + G3(maskW, i + 1, j, k) + G3(maskW, i, j - 1, k) + G3(maskW, i + 1, j - 1, k));
         gV = gV + fvFac * c;
       }
-      if (PART != 2 && p.select3dCoriScheme >= 1) {
+      if (PART != 2 && O::cori3d(p)) {
         // MOM_U_CORIOLIS_NH (pkg/mom_common/mom_u_coriolis_nh.F:60-76), angleCosC = 1; the V
         // component only on curvilinear / rotated grids (mom_fluxform.F:1025-1040)
         const int kp1 = k + 1 < Nr ? k + 1 : Nr;
@@ -1100,7 +1101,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
     }
     // ---------------- TIMESTEP (timestep.F:104-388)
     double guExt = 0.0, gvExt = 0.0;
-    if (p.momForcing && k == 1) {
+    if (O::momForcing(p) && k == 1) {
       // APPLY_FORCING_U/V (apply_forcing.F:81-88) on j=0..sNy+1,i=1..sNx+1 (U) / i=0..sNx+1,j=1..sNy+1 (V)
       if (j >= 0 && j <= d.sNy + 1 && i >= 1 && i <= d.sNx + 1)
         guExt = guExt + p.foFacMom * (AR2(fu, q2) * mass2rUnit) * recip_drF * G3(recip_hFacW, i, j, k);
@@ -1111,8 +1112,8 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
       // timestep.F:116-126 synchronous time step: gU -= phFac*dPhiHydX
       gU = gU - p.pfFacMom * dPhiHydX;
       gV = gV - p.pfFacMom * dPhiHydY;
-      if (p.momViscosity && p.momDissip_In_AB) { gU = gU + guDiss; gV = gV + gvDiss; }
-      if (p.momForcing && p.momForcingOutAB != 1) { gU = gU + guExt; gV = gV + gvExt; }
+      if (O::momViscosity(p) && O::dissipInAB(p)) { gU = gU + guDiss; gV = gV + gvDiss; }
+      if (O::momForcing(p) && !O::forcingOutAB(p)) { gU = gU + guExt; gV = gV + gvExt; }
     }
     // ADAMS_BASHFORTH2 over the whole halo-inclusive slab (adams_bashforth2.F:81-88)
     const long q3 = MG_I3(d, i, j, k, t);
@@ -1128,10 +1129,10 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
     double gUtmp = 0.0, gVtmp = 0.0;   // timestep.F local arrays: 0 outside iMin..iMax, jMin..jMax
     if (inner) {
       gUtmp = gU; gVtmp = gV;
-      if (p.momForcing && p.momForcingOutAB == 1) { gUtmp = gUtmp + guExt; gVtmp = gVtmp + gvExt; }
-      if (p.momViscosity && !p.momDissip_In_AB) { gUtmp = gUtmp + guDiss; gVtmp = gVtmp + gvDiss; }
-      if (!p.useCDscheme) {
-        if (rstar && p.nonlinFreeSurf > 1) {   // timestep.F:274-284
+      if (O::momForcing(p) && O::forcingOutAB(p)) { gUtmp = gUtmp + guExt; gVtmp = gVtmp + gvExt; }
+      if (O::momViscosity(p) && !O::dissipInAB(p)) { gUtmp = gUtmp + guDiss; gVtmp = gVtmp + gvDiss; }
+      if (!O::cdScheme(p)) {
+        if (rstar && O::nlfs2(p)) {   // timestep.F:274-284
           gUtmp = gUtmp / G2(rStarExpW, i, j);
           gVtmp = gVtmp / G2(rStarExpS, i, j);
         }
@@ -1140,7 +1141,7 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
         gV = V(i, j, k) + p.deltaTMom * (gVtmp + 0.0) * G3(maskS, i, j, k);
       }
     }
-    if (p.useCDscheme) {   // k_cd_scheme finishes u*
+    if (O::cdScheme(p)) {   // k_cd_scheme finishes u*
       if (COMP != 2) AR3(cdU, q3) = gUtmp;
       if (COMP != 1) AR3(cdV, q3) = gVtmp;
     }
@@ -1153,11 +1154,11 @@ __device__ __forceinline__ void mom_step_ijz(const Dims &d, const Params &p, con
 #undef G2
 #undef G3
 }
-template <bool VI, int COMP>
+template <bool VI, int COMP, class O = OptsRun>
 __device__ __forceinline__ void mom_step_point(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
                                                int lblock) {
   MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lblock)
-  mom_step_ijz<VI, COMP>(d, p, f, iterPtr, i, j, z, true, nullptr);
+  mom_step_ijz<VI, COMP, 0, O>(d, p, f, iterPtr, i, j, z, true, nullptr);
 }
 // MOM_FLUXFORM + TIMESTEP + AB2 with four threads per point: wave 0 the U component's
 // advective / metric / Coriolis / pressure terms, wave 1 its viscous terms, waves 2, 3 the
@@ -1212,6 +1213,7 @@ __global__ void __launch_bounds__(256) k_mom_step_uv(Dims d, Params p, Fields f,
 // guCor/gvCor added to gUtmp/gVtmp (cdU/cdV from k_mom_step), and u* formed on the
 // TIMESTEP range 0..sN+1.  uNM1/vNM1 = u, v is done by k_sfp_rhs (after this kernel,
 // whose neighbours still read the old values).
+template <class O = OptsRun>
 __device__ __forceinline__ void cd_scheme_body(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
                                                int lb) {
   MG_PLANE_LB(2 - d.OLx, d.nx - 2, 2 - d.OLy, d.ny - 2, z, lb)
@@ -1253,7 +1255,7 @@ __device__ __forceinline__ void cd_scheme_body(const Dims &d, const Params &p, c
   const double gvCor = -(G2(fCori, i, j) + G2(fCori, i, j - 1)) * 0.5 * uD * p.cfFacMom;
   if (i >= 0 && i <= d.sNx + 1 && j >= 0 && j <= d.sNy + 1) {
     double gUtmp = AR3(cdU, q3) + guCor, gVtmp = AR3(cdV, q3) + gvCor;
-    if (p.nonlinFreeSurf > 1 && p.select_rStar > 0) {   // timestep.F:274-284
+    if (O::nlfs2(p) && O::rstarOn(p)) {   // timestep.F:274-284
       gUtmp = gUtmp / G2(rStarExpW, i, j);
       gVtmp = gVtmp / G2(rStarExpS, i, j);
     }

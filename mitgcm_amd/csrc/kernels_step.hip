@@ -131,15 +131,37 @@ static void launch_l1(const Dims &d, const Params &p, const Fields &f, int nbDel
   hipLaunchKernelGGL(k_dt_l1, dim3((unsigned)(nbOp + nbGm + nbPhi + nbDel)), dim3(256), mg_colf_lds(d.Nr, nc, nArr), s, d, p,
                      f, nc, nbGm, nbPhi, nbOp, dt_long_first());
 }
-template <bool GM, bool FF4>
+// O: the option set the momentum and tracer bodies are compiled for (common.h; OptsGO90 where
+// the plan says so, StepPlan::spec)
+template <bool GM, bool FF4, class O = OptsRun>
 __global__ void __launch_bounds__(256) k_dt_l2(Dims d, Params p, Fields f, TracerArgs aT, TracerArgs aS,
                                                const int *iterPtr, int nbMom, int nbTr, const long *__restrict__ srcOf,
                                                int nbPc, int nbOp, int lf) {
   int lb = mg_xcd_block();
+  if constexpr (O::pinned) {
+    // one inlined copy of the right-hand side for both tracers and both block orders (the
+    // TracerArgs are selected, not the code: a quarter of the tracer instructions to fetch cold)
+    const int head = nbPc + nbOp + nbMom;
+    const int lt = lf ? (lb < 2 * nbTr ? lb : -1) : lb - head;   // the tracers' block, or < 0
+    if (lt >= 0) {
+      const bool salt = lt >= nbTr;
+      tracer_rhs_body_br<GM, O>(d, p, f, salt ? aS : aT, iterPtr, salt ? lt - nbTr : lt);
+      return;
+    }
+    if (lf) lb -= 2 * nbTr;
+    if (lb < nbPc) { ucg2d_p_point(d, p, f, srcOf, lb); return; }
+    lb -= nbPc;
+    if (lb < nbOp) { ucg2d_op_point(d, p, f, lb); return; }
+    lb -= nbOp;
+    static_assert(!(O::pinned && FF4), "the pinned bodies are the U / V halves");
+    if (lb & 1) mom_step_point<false, 2, O>(d, p, f, iterPtr, lb >> 1);
+    else mom_step_point<false, 1, O>(d, p, f, iterPtr, lb >> 1);
+    return;
+  }
   if (lf) {   // long first: the tracers' right-hand sides at the head of the dispatch
     if (lb < 2 * nbTr) {
-      if (lb < nbTr) tracer_rhs_body_br<GM>(d, p, f, aT, iterPtr, lb);
-      else tracer_rhs_body_br<GM>(d, p, f, aS, iterPtr, lb - nbTr);
+      if (lb < nbTr) tracer_rhs_body_br<GM, O>(d, p, f, aT, iterPtr, lb);
+      else tracer_rhs_body_br<GM, O>(d, p, f, aS, iterPtr, lb - nbTr);
       return;
     }
     lb -= 2 * nbTr;
@@ -150,18 +172,31 @@ __global__ void __launch_bounds__(256) k_dt_l2(Dims d, Params p, Fields f, Trace
   lb -= nbOp;
   if (lb < nbMom) {
     if constexpr (FF4) mom_ff4_body(d, p, f, iterPtr, lb);
-    else if (lb & 1) mom_step_point<false, 2>(d, p, f, iterPtr, lb >> 1);
-    else mom_step_point<false, 1>(d, p, f, iterPtr, lb >> 1);
+    else if (lb & 1) mom_step_point<false, 2, O>(d, p, f, iterPtr, lb >> 1);
+    else mom_step_point<false, 1, O>(d, p, f, iterPtr, lb >> 1);
     return;
   }
   lb -= nbMom;
-  if (lb < nbTr) tracer_rhs_body_br<GM>(d, p, f, aT, iterPtr, lb);
-  else tracer_rhs_body_br<GM>(d, p, f, aS, iterPtr, lb - nbTr);
+  if (lb < nbTr) tracer_rhs_body_br<GM, O>(d, p, f, aT, iterPtr, lb);
+  else tracer_rhs_body_br<GM, O>(d, p, f, aS, iterPtr, lb - nbTr);
 }
+template <class O = OptsRun>
 __global__ void __launch_bounds__(256) k_dt_l3(Dims d, Params p, Fields f, TracerArgs aT, TracerArgs aS,
                                                const int *iterPtr, int nc, int nbCd, int nbImp, const long *__restrict__ srcOf,
                                                int nbPc, int lf) {
   int lb = mg_xcd_block();
+  if constexpr (O::pinned) {   // one inlined copy of the implicit solve (k_dt_l2)
+    const int lt = lf ? (lb < 2 * nbImp ? lb : -1) : lb - (nbPc + nbCd);   // the solves' block, or < 0
+    if (lt >= 0) {
+      const bool salt = lt >= nbImp;
+      tracer_impl_body<false, O>(d, p, f, salt ? aS : aT, nc, salt ? lt - nbImp : lt);
+      return;
+    }
+    if (lf) lb -= 2 * nbImp;
+    if (lb < nbPc) { ucg2d_p_point(d, p, f, srcOf, lb); return; }
+    cd_scheme_body<O>(d, p, f, iterPtr, lb - nbPc);
+    return;
+  }
   if (lf) {   // long first: the implicit solves' column sweeps at the head of the dispatch
     if (lb < 2 * nbImp) {
       if (lb < nbImp) tracer_impl_body<false>(d, p, f, aT, nc, lb);
@@ -195,6 +230,14 @@ bool dyn_thermo_fusable(const Dims &d, const Params &p, const TracerArgs &aT, co
   return mg_hfuse(MG_FUSE_DT, d.nx, d.ny, d.nT, d.Nr) && p.momStepping && p.tempStepping && p.saltStepping &&
          p.useGMRedi && p.implicitDiffusion && !aT.multiDim && !aS.multiDim && !p.vectorInvariantMomentum &&
          aT.scr != aS.scr && aT.scheme == 2 && aS.scheme == 2 && !p.useAB3;   // (tracer_rhs_body_br: C2, AB2)
+}
+
+// Where the fold's grids may run the bodies compiled for the pinned option set (common.h
+// OptsGO90): the model's options are that set (opts_match), the default layout with the U / V
+// momentum halves runs (the instantiations that exist), and MGCM_STEP_FUSE bit MG_FUSE_SPEC.
+// With dyn_thermo_fusable, which plan_step tests beside it
+bool dyn_thermo_spec_ok(const Params &p) {
+  return mg_fuse_on(MG_FUSE_SPEC) && opts_match(p) && dyn_thermo_takes_gm(p) && !mom_ff4_on(true);
 }
 
 // CALC_PHI_HYD's column frame as launch_phi_hyd sizes it
@@ -264,9 +307,10 @@ hipError_t launch_tracer_hpair(const Dims &d, const Params &p, const Fields &f, 
 // launch_update_r_star_cg2d then runs with opEarly.  gmHere = false (the default layout only):
 // GMREDI_CALC_TENSOR of this step ran in the previous step's grids.  l1Here = false (with it):
 // so did CALC_PHI_HYD and del2uv (k_rstar_exch_phi, or launch_phi_del2 at the head of a call) --
-// two launches
+// two launches.  spec (the default layout only, StepPlan::spec): k_dt_l2's and k_dt_l3's bodies
+// compiled for the pinned option set (common.h OptsGO90)
 hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, const TracerArgs &aT, const TracerArgs &aS,
-                             const int *iterPtr, hipStream_t s, const long *srcOf, bool gmHere, bool l1Here) {
+                             const int *iterPtr, hipStream_t s, const long *srcOf, bool gmHere, bool l1Here, bool spec) {
   const dim3 blk(256);
   // front: phi's column frame (launch_phi_hyd's columns and LDS), del2uv's and the tracers' planes
   int ncPhi, nArrPhi, nbPhi;
@@ -285,19 +329,24 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
     else if (gmHere) return hipErrorInvalidValue;
     const bool ff4 = mom_ff4_on(true);
     const int nbMom = ff4 ? mom_ff4_blocks(d) : 2 * (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
-    auto l2 = ff4 ? k_dt_l2<true, true> : k_dt_l2<true, false>;
+    if (spec && (ff4 || !opts_match(p))) return hipErrorInvalidValue;   // (the plan pins only what matches)
+    auto l2 = ff4 ? k_dt_l2<true, true> : spec ? k_dt_l2<true, false, OptsGO90> : k_dt_l2<true, false>;
     hipLaunchKernelGGL(l2, dim3((unsigned)(nbPc2 + nbOp2 + nbMom + 2 * nbTr)), blk, 0, s, d, p, f, aT, aS, iterPtr, nbMom, nbTr,
                        srcOf, nbPc2, nbOp2, dt_long_first());
     const long ncolTr = (long)d.sNx * d.sNy * d.nT;
     const int ncTr = mg_colf_nc(ncolTr, d.Nr, 3);
     const int nbImp = (int)mg_colf_blocks(ncolTr, ncTr);
     const int nbCd = (int)mg_plane_blocks(d.nx - 2, d.ny - 2, d.nT * d.Nr);
-    MG_ALLOW_LDS(k_dt_l3);
-    hipLaunchKernelGGL(k_dt_l3, dim3((unsigned)(nbPc3 + nbCd + 2 * nbImp)), blk, mg_colf_lds(d.Nr, ncTr, 3), s, d, p, f, aT,
+    MG_ALLOW_LDS(k_dt_l3<OptsRun>);
+    MG_ALLOW_LDS(k_dt_l3<OptsGO90>);
+    // (both grids took their pinned instantiation by measurement: 22.2 -> 20.0 and 13.6 -> 10.7 us,
+    // profiles/r14/step_spec/)
+    auto l3 = spec ? k_dt_l3<OptsGO90> : k_dt_l3<OptsRun>;
+    hipLaunchKernelGGL(l3, dim3((unsigned)(nbPc3 + nbCd + 2 * nbImp)), blk, mg_colf_lds(d.Nr, ncTr, 3), s, d, p, f, aT,
                        aS, iterPtr, ncTr, nbCd, nbImp, srcOf, nbPc3, dt_long_first());
     return hipGetLastError();
   }
-  if (srcOf || !gmHere || !l1Here) return hipErrorInvalidValue;   // (the operator rides, and the tensor and grid 1 leave, only in the default layout)
+  if (srcOf || !gmHere || !l1Here || spec) return hipErrorInvalidValue;   // (the operator rides, and the tensor and grid 1 leave, only in the default layout)
   MG_ALLOW_LDS(k_dt_front<true>);
   hipLaunchKernelGGL(k_dt_front<true>, dim3((unsigned)(nbPhi + nbDel + 2 * nbTr)), blk,
                      mg_colf_lds(d.Nr, ncPhi, nArrPhi), s, d, p, f, aT, aS, iterPtr, ncPhi, nbPhi, nbDel, nbTr);

@@ -448,7 +448,7 @@ __global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a
 // the fused kernel from 125 to 196 VGPRs (4 -> 2 waves per SIMD) and C2 measured 1.5 %
 // slower (0.2901 against 0.2852 ms/step); capping the kernel at 128 spills
 // (profiles/r05/gm_loads/). Same arithmetic, bit-identical results.
-template <bool GM>
+template <bool GM, class O = OptsRun>
 __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a,
                                                 const int *iterPtr, int lb) {
   MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
@@ -468,7 +468,7 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
   const double drF = f.drF[k - 1];
   // uFld, vFld, wFld of thermodynamics.F:252-268: the Eulerian velocity plus, with
   // GM_AdvForm, GMREDI_RESIDUAL_FLOW's bolus velocity (gmredi_residual_flow.F:58-97)
-  const bool bolus = GM && p.GM_AdvForm;
+  const bool bolus = GM && O::gmAdvForm(p);
   const double flip = -p.gravitySign;
   const int kp1b = k + 1 < Nr ? k + 1 : Nr;
   const double maskp1b = k >= Nr ? 0.0 : 1.0;
@@ -519,7 +519,7 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
     if (a.diffKh != 0.0) df = -a.diffKh * xA * G2(recip_dxC, ii, j) * (T3(ii, j, k) - T3(ii - 1, j, k));
     if (GM)   // GMREDI_XTRANSPORT (gmredi_xtransport.F:94-101)
       df = df - xA * G3(Kux, ii, j, k) * G2(recip_dxC, ii, j) * (T3(ii, j, k) - T3(ii - 1, j, k));
-    if (GM && p.GM_ExtraDiag) df = df - xA * G3(Kuz, ii, j, k) * gm_dTdz(ii, j, 0);
+    if (GM && O::gmExtraDiag(p)) df = df - xA * G3(Kuz, ii, j, k) * gm_dTdz(ii, j, 0);
     return fz + df;
   };
   auto fmer = [&](int jj) {
@@ -530,7 +530,7 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
     if (a.diffKh != 0.0) df = -a.diffKh * yA * G2(recip_dyC, i, jj) * (T3(i, jj, k) - T3(i, jj - 1, k));
     if (GM)   // GMREDI_YTRANSPORT
       df = df - yA * G3(Kvy, i, jj, k) * G2(recip_dyC, i, jj) * (T3(i, jj, k) - T3(i, jj - 1, k));
-    if (GM && p.GM_ExtraDiag) df = df - yA * G3(Kvz, i, jj, k) * gm_dTdz(i, jj, 1);
+    if (GM && O::gmExtraDiag(p)) df = df - yA * G3(Kvz, i, jj, k) * gm_dTdz(i, jj, 1);
     return fm + df;
   };
   // CALC_ADV_FLOW rTrans of level kk (0 at the surface and below the bottom level)
@@ -548,7 +548,7 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
       fv = fv + wT * maskInC;
     }
     double dfr = 0.0;
-    if (!p.implicitDiffusion && kk >= 2 && kk <= Nr) {
+    if (!O::implicitDiffusion(p) && kk >= 2 && kk <= Nr) {
       double kap = (G3(IVDConvCount, i, j, kk) * p.ivdc_kappa + 0.0) + a.diffKr;
       if (GM) kap = kap + G3(Kwz, i, j, kk) * maskInC;
       const double maskUp = G3(maskC, i, j, kk - 1) * G3(maskC, i, j, kk);
@@ -586,20 +586,20 @@ __device__ __forceinline__ void tracer_rhs_body_br(const Dims &d, const Params &
                         Tk * ((uT1 - uT0) * advFac + (vT1 - vT0) * advFac + (rTransKp - rTrans) * rAdvFac) * maskInC);
   double gtForc = 0.0;
   if (a.forcing && a.sfc && k == 1) gtForc = gtForc + a.sfc[q] * f.recip_drF[0] * f.recip_hFacC[q3];
-  if (!p.tracForcingOutAB) gT = gT + gtForc;   // inside (0) / after (1) AB2: temp_integrate.F:373-410
+  if (!O::tracForcingOutAB(p)) gT = gT + gtForc;   // inside (0) / after (1) AB2: temp_integrate.F:373-410
   if (a.useAB) {   // ADAMS_BASHFORTH2(k)
     const double ab = abFac * (gT - a.gNm1[q3]);
     double gN = gT;
     gT = gT + ab;
     // FREESURF_RESCALE_G of gT and gtNm1 under r* (temp_integrate.F:412-446)
-    if (p.nonlinFreeSurf > 0 && p.select_rStar > 0) gN = gN / f.rStarExpC[q];
+    if (O::rstar(p)) gN = gN / f.rStarExpC[q];
     a.gNm1[q3] = gN;
   }
-  if (p.tracForcingOutAB) gT = gT + gtForc;
-  if (p.nonlinFreeSurf > 0 && p.select_rStar > 0) gT = gT / f.rStarExpC[q];
+  if (O::tracForcingOutAB(p)) gT = gT + gtForc;
+  if (O::rstar(p)) gT = gT / f.rStarExpC[q];
   // TIMESTEP_TRACER
   const double v = Tk + p.deltaTtracer * gT;
-  if (p.implicitDiffusion) a.scr[q3] = v;
+  if (O::implicitDiffusion(p)) a.scr[q3] = v;
   else a.trNext[q3] = v;   // CYCLE_TRACER directly
 #undef T3
 #undef G2
@@ -1203,7 +1203,7 @@ __global__ void __launch_bounds__(256) k_tracer_rhs_flat(Dims d, Params p, Field
 // kernel on deep columns: LLC-90 1.226-1.241 against 1.265-1.267 ms/step with the tracer
 // march's hoisted factors, profiles/r05/tracer_loads/); the fused C2 / C3 kernels keep the
 // branch form (0.3-0.9 % slower there with UL, more VGPRs for the few levels each thread forms)
-template <bool UL>
+template <bool UL, class O = OptsRun>
 __device__ __forceinline__ void tracer_impl_body(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a, int nc,
                                                  int lb) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -1213,7 +1213,7 @@ __device__ __forceinline__ void tracer_impl_body(const Dims &d, const Params &p,
 #define G3(a_, ii, jj, kk_) f.a_[MG_I3(d, ii, jj, kk_, t)]
   if (valid) {
     // recip_hFacNew (thermodynamics.F:198-210): recip_hFacC/rStarExpC under r*
-    const bool rs = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
+    const bool rs = O::rstar(p);
     const long q2 = MG_I2(d, i, j, t);
     const double rsx = rs ? f.rStarExpC[q2] : 1.0;
     const double mIn = f.maskInC[q2];

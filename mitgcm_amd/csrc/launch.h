@@ -60,7 +60,8 @@ hipError_t launch_gm_residual_flow(const Dims &, const Params &, const Fields &,
 // ---- kernels_step.hip
 bool dyn_thermo_fusable(const Dims &, const Params &, const TracerArgs &, const TracerArgs &);
 hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const TracerArgs &, const TracerArgs &, const int *,
-                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true);
+                             hipStream_t, const long *srcOf = nullptr, bool gmHere = true, bool l1Here = true, bool spec = false);
+bool dyn_thermo_spec_ok(const Params &);
 bool phi_pipe_ok(const Dims &, const Params &);
 hipError_t launch_phi_del2(const Dims &, const Params &, const Fields &, hipStream_t);
 hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, const long *, const XFields &, const long *, int,

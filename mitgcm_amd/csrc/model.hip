@@ -2170,6 +2170,10 @@ struct StepPlan {
   // against the scheme-2 right-hand side, which reads Psi one point outside the interior at
   // most, and the residual flow reads it over the whole slab
   bool resFlow, resFlowFold;
+  // the fold's second and third grid run the bodies compiled for the pinned option
+  // set (common.h OptsGO90, MG_FUSE_SPEC): the model's options are that set and the fold's default
+  // layout runs (dyn_thermo_spec_ok).  A choice of instantiation only: the same launches, the same bits
+  bool spec;
 };
 static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const Params &p = m->p;
@@ -2193,6 +2197,7 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   pl.dtFused = pl.forkable && pl.rstar && dyn_thermo_fusable(d, p, tracer_args(m, false), tracer_args(m, true));
   // (GMREDI_CALC_TENSOR in launch_dyn_thermo's first grid when it takes it)
   const bool gmFold = pl.dtFused && dyn_thermo_takes_gm(p);
+  pl.spec = gmFold && dyn_thermo_spec_ok(p);
   pl.forkEarly = pl.fork && !pl.thermoLate && !pl.dtFused;
   pl.thermoInline = !pl.stagger && !pl.fork && !pl.dtFused;
   pl.gmPhi = (pl.stagger || pl.thermoLate) && !pl.dtFused && !m->timing && gm_phi_fusable(d, p);
@@ -2224,11 +2229,12 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
 }
 // mgcm_get_param("stepLayout") (model.py step_layout): bit 0 THERMODYNAMICS folded into
 // DYNAMICS' grids (k_dt_l1/l2/l3), 2 the tracers on the second stream, 3 joined only before the
-// correction step, 4 pipelined, 5 with the next step's CALC_PHI_HYD too; bit 1 is retired
+// correction step, 4 pipelined, 5 with the next step's CALC_PHI_HYD too, 6 (value 64) the fold's
+// bodies compiled for the pinned option set; bit 1 is retired
 // (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
 static int step_layout_bits(const StepPlan &pl) {
   return (pl.dtFused ? 1 : 0) | (pl.forkable && !pl.dtFused ? 4 : 0) | (pl.forkable && pl.forkLate ? 8 : 0) |
-         (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0);
+         (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0) | (pl.spec ? 64 : 0);
 }
 
 // THERMODYNAMICS onto the second stream (after the model stream's work so far), evJoin behind
@@ -2262,7 +2268,7 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
   if (pl.mom) {
     if (pl.dtFused) {
       TIMED(K_MOM, launch_dyn_thermo(m->d, m->p, m->f, tracer_args(m, false), tracer_args(m, true), m->d_ctr, m->stream,
-                                     pl.opEarly ? m->d_srcOf : nullptr, !pl.pipe, !pl.phiPipe));
+                                     pl.opEarly ? m->d_srcOf : nullptr, !pl.pipe, !pl.phiPipe, pl.spec));
       std::swap(m->f.theta, m->f.thetaNext);   // CYCLE_TRACER: the new tracers are the other buffers
       std::swap(m->f.salt, m->f.saltNext);
       // PTRACERS_INTEGRATE where the fold replaced tracers_on: right behind it, before
