@@ -448,8 +448,8 @@ template <class A> __device__ __forceinline__ double vi_h0S_own(const A &a, int 
 
 // ---- MOM_VECINV's per-level intermediates as functions of an accessor A of the level's
 // 3-D fields (uVel, vVel, hFacW, hFacS, recip_hFacC at (ii, jj, k)): VIGlobal reads them
-// from HBM, VITile from the LDS-staged tile of k_mom_vi_tiled; the expression trees are
-// shared, so both kernels produce the same bits.
+// from HBM, the staged accessors (VILevel, VIMarch, VIM2) from the LDS-staged level of their
+// kernels; the expression trees are shared, so every kernel produces the same bits.
 // hFacZ (pkg/mom_common/mom_calc_hfacz.F:158-225, hZoption = 0)
 template <class A>
 __device__ __forceinline__ double vi_hfacz(const A &a, const Dims &d, int ii, int jj, int k) {
@@ -1270,277 +1270,130 @@ __global__ void __launch_bounds__(256) k_cd_scheme(Dims d, Params p, Fields f, c
 }
 
 // ---------------------------------------------------------------------------------------
-// MOM_VECINV + CALC_GRAD_PHI_HYD + TIMESTEP + ADAMS_BASHFORTH2 as a 2.5-D tiled sweep: one
-// workgroup owns a BX x BY block of the DYNAMICS range 0..sN+1 of one tile and marches
-// k = 1..Nr.  The level fields the stencils reach (u, v, w, hFacW, hFacS, hFacC on the
-// block plus one ring) are staged in LDS once per level: u, v, hFac in three rotating
-// slots (levels k-1, k, k+1: the vertical shear and the vertical viscous fluxes), w in
-// two; level k+1 is loaded while level k's intermediates are formed.  KE, vort3, hFacZ,
-// h0FacZ and hDiv are formed once per point of the block's (BX+1) x (BY+1) grid into LDS
-// instead of being re-derived by every neighbour.  Masks and reciprocal hFacs come from
-// the staged hFac (maskW = hFacW != 0, recip_hFacW = 1/hFacW: ini_masks_etc.F and
-// update_r_star.F define them so).  vecinv_tend is the same template as the per-point
-// kernel's (accessor VITile), so the two kernels agree bit for bit.
+// MOM_VECINV + CALC_GRAD_PHI_HYD + TIMESTEP + ADAMS_BASHFORTH2 on LDS-staged levels: one
+// workgroup owns a BX x BY block of the DYNAMICS range 0..sN+1 of one tile.  The level
+// fields the stencils reach (u, v, w, hFacW, hFacS, hFacC on the block plus one ring) are
+// staged in LDS; KE, vort3, hFacZ, h0FacZ and hDiv are formed once per point of the block's
+// (BX+1) x (BY+1) grid into LDS instead of being re-derived by every neighbour
+// (vi_intermediates).  Masks and reciprocal hFacs come from the staged hFac (maskW =
+// hFacW != 0, recip_hFacW = 1/hFacW: ini_masks_etc.F and update_r_star.F define them so).
+// vecinv_tend is the same template as the per-point kernel's, so every form agrees with it
+// bit for bit.  Three forms: one level per workgroup (k_mom_vi_level, accessor VILevel), the
+// register-pipelined k-march (k_mom_vi_march, VIMarch) and the k-march specialised at
+// compile time (k_mom_vi_m2, VIM2).  An accessor states where a level's value comes from
+// (uVel, vVel, wVel, hFacW/S/C (ii, jj, kk), g (ii, jj, kk), g2<F> (ii, jj), i0, j0, IW and
+// the LDS pointers); VIStaged derives the rest.
 constexpr int VT_NT = 256, VT_EMAX = 352, VT_IMAX = 304;
 
-struct VITile {
-  const Dims &d; const Params &p; const Fields &f; int k, t, i0, j0, EW, IW;
-  const double *sU, *sV, *sW, *sHW, *sHS, *sHC;   // [3][EMAX] / w [2][EMAX]
-  const double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;   // [IMAX]
-  __device__ __forceinline__ int e(int ii, int jj) const { return (jj - j0 + 1) * EW + (ii - i0 + 1); }
-  template <int F> __device__ __forceinline__ double g2(int ii, int jj) const { return f.a2[(long)F * d.N2all + MG_I2(d, ii, jj, t)]; }
-  __device__ __forceinline__ int sl(int kk) const { return (kk % 3) * VT_EMAX; }
-  __device__ __forceinline__ double uVel(int ii, int jj, int kk) const { return sU[sl(kk) + e(ii, jj)]; }
-  __device__ __forceinline__ double vVel(int ii, int jj, int kk) const { return sV[sl(kk) + e(ii, jj)]; }
-  __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return sW[(kk & 1) * VT_EMAX + e(ii, jj)]; }
-  __device__ __forceinline__ double hFacW(int ii, int jj, int kk) const { return sHW[sl(kk) + e(ii, jj)]; }
-  __device__ __forceinline__ double hFacS(int ii, int jj, int kk) const { return sHS[sl(kk) + e(ii, jj)]; }
-  __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return sHC[sl(kk) + e(ii, jj)]; }
-  __device__ __forceinline__ double maskW(int ii, int jj, int kk) const { return hFacW(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskS(int ii, int jj, int kk) const { return hFacS(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskC(int ii, int jj, int kk) const { return hFacC(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
+struct VIMarchRegs {   // the output point's own 2-D values (i,j); n = (i,j+1), e = (i+1,j), w = (i-1,j), s = (i,j-1)
+  double recip_dxC, recip_dyC, recip_dxG, recip_dyG, rAw, rAs, recip_rAw, recip_rAs;
+  double dxV, dxVn, recip_dyU, recip_dyUn, dyU, dyUe, recip_dxV, recip_dxVe;
+  double fCoriG, fCoriGn, fCoriGe, rA, rAw_w, rA_s;
+  __device__ __forceinline__ void load(const Dims &d, const Fields &f, const long q2) {
+    const long qn = q2 + d.nx, qe = q2 + 1, qw = q2 - 1, qs = q2 - d.nx;
+    recip_dxC = AR2(recip_dxC, q2); recip_dyC = AR2(recip_dyC, q2);
+    recip_dxG = AR2(recip_dxG, q2); recip_dyG = AR2(recip_dyG, q2);
+    rAw = AR2(rAw, q2); rAs = AR2(rAs, q2); recip_rAw = AR2(recip_rAw, q2); recip_rAs = AR2(recip_rAs, q2);
+    dxV = AR2(dxV, q2); dxVn = AR2(dxV, qn); recip_dyU = AR2(recip_dyU, q2); recip_dyUn = AR2(recip_dyU, qn);
+    dyU = AR2(dyU, q2); dyUe = AR2(dyU, qe); recip_dxV = AR2(recip_dxV, q2); recip_dxVe = AR2(recip_dxV, qe);
+    fCoriG = AR2(fCoriG, q2); fCoriGn = AR2(fCoriG, qn); fCoriGe = AR2(fCoriG, qe);
+    rA = AR2(rA, q2); rAw_w = AR2(rA, qw); rA_s = AR2(rA, qs);
+  }
+};
+constexpr int VM_S2 = 6;  // LDS-staged 2-D fields: dxC, dyC, recip_rAz, dxG, dyG, recip_rA
+
+template <class A>
+struct VIStaged {
+  __device__ __forceinline__ const A &s() const { return static_cast<const A &>(*this); }
+  __device__ __forceinline__ double maskW(int ii, int jj, int kk) const { return s().hFacW(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
+  __device__ __forceinline__ double maskS(int ii, int jj, int kk) const { return s().hFacS(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
+  __device__ __forceinline__ double maskC(int ii, int jj, int kk) const { return s().hFacC(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
   __device__ __forceinline__ double recip_hFacW(int ii, int jj, int kk) const {
-    const double h = hFacW(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
+    const double h = s().hFacW(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
   __device__ __forceinline__ double recip_hFacS(int ii, int jj, int kk) const {
-    const double h = hFacS(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
+    const double h = s().hFacS(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
   __device__ __forceinline__ double recip_hFacC(int ii, int jj, int kk) const {
-    const double h = hFacC(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double h0FacW(int ii, int jj, int kk) const { return AR3(h0FacW, MG_I3(d, ii, jj, kk, t)); }
-  __device__ __forceinline__ double h0FacS(int ii, int jj, int kk) const { return AR3(h0FacS, MG_I3(d, ii, jj, kk, t)); }
-  __device__ __forceinline__ int iv(int ii, int jj) const { return (jj - j0) * IW + (ii - i0); }       // vort grid
-  __device__ __forceinline__ int id(int ii, int jj) const { return (jj - j0 + 1) * IW + (ii - i0 + 1); } // hDiv grid
-  __device__ __forceinline__ double hfz(int ii, int jj) const { return sHfz[iv(ii, jj)]; }
-  __device__ __forceinline__ double h0fz(int ii, int jj) const { return sH0fz[iv(ii, jj)]; }
-  __device__ __forceinline__ double vort(int ii, int jj) const { return sVort[iv(ii, jj)]; }
-  __device__ __forceinline__ double KE(int ii, int jj) const { return sKE[id(ii, jj)]; }
-  __device__ __forceinline__ double hDiv(int ii, int jj) const { return sHDiv[id(ii, jj)]; }
+    const double h = s().hFacC(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
+  __device__ __forceinline__ double h0FacW(int ii, int jj, int kk) const {
+    const Dims &d = s().d; const Fields &f = s().f; return AR3(h0FacW, s().g(ii, jj, kk)); }
+  __device__ __forceinline__ double h0FacS(int ii, int jj, int kk) const {
+    const Dims &d = s().d; const Fields &f = s().f; return AR3(h0FacS, s().g(ii, jj, kk)); }
+  __device__ __forceinline__ int iv(int ii, int jj) const { return (jj - s().j0) * s().IW + (ii - s().i0); }       // vort grid
+  __device__ __forceinline__ int id(int ii, int jj) const { return (jj - s().j0 + 1) * s().IW + (ii - s().i0 + 1); } // hDiv grid
+  __device__ __forceinline__ double hfz(int ii, int jj) const { return s().sHfz[iv(ii, jj)]; }
+  __device__ __forceinline__ double h0fz(int ii, int jj) const { return s().sH0fz[iv(ii, jj)]; }
+  __device__ __forceinline__ double vort(int ii, int jj) const { return s().sVort[iv(ii, jj)]; }
+  __device__ __forceinline__ double KE(int ii, int jj) const { return s().sKE[id(ii, jj)]; }
+  __device__ __forceinline__ double hDiv(int ii, int jj) const { return s().sHDiv[id(ii, jj)]; }
+  // g2<F> of the march accessors: the VM_S2 fields staged in s2 (ES: elements per field), with
+  // OWN the output point's own metrics from its VIMarchRegs c, anything else where it lies
+  template <int F, bool OWN> __device__ __forceinline__ double g2_march(int ES, int ii, int jj) const {
+    const A &a = s();
+    if constexpr (F == F2_dxC) return a.s2[0 * ES + a.e(ii, jj)];
+    else if constexpr (F == F2_dyC) return a.s2[1 * ES + a.e(ii, jj)];
+    else if constexpr (F == F2_recip_rAz) return a.s2[2 * ES + a.e(ii, jj)];
+    else if constexpr (F == F2_dxG) return a.s2[3 * ES + a.e(ii, jj)];
+    else if constexpr (F == F2_dyG) return a.s2[4 * ES + a.e(ii, jj)];
+    else if constexpr (F == F2_recip_rA) return a.s2[5 * ES + a.e(ii, jj)];
+    else {
+      if constexpr (OWN) {
+        const int di = ii - a.i, dj = jj - a.j;
+#define VM_R(name, DI, DJ, reg) if constexpr (F == F2_##name) { if (di == (DI) && dj == (DJ)) return a.c.reg; }
+        VM_R(recip_dxC, 0, 0, recip_dxC) VM_R(recip_dyC, 0, 0, recip_dyC) VM_R(recip_dxG, 0, 0, recip_dxG)
+        VM_R(recip_dyG, 0, 0, recip_dyG) VM_R(rAw, 0, 0, rAw) VM_R(rAs, 0, 0, rAs) VM_R(recip_rAw, 0, 0, recip_rAw)
+        VM_R(recip_rAs, 0, 0, recip_rAs) VM_R(dxV, 0, 0, dxV) VM_R(dxV, 0, 1, dxVn) VM_R(recip_dyU, 0, 0, recip_dyU)
+        VM_R(recip_dyU, 0, 1, recip_dyUn) VM_R(dyU, 0, 0, dyU) VM_R(dyU, 1, 0, dyUe) VM_R(recip_dxV, 0, 0, recip_dxV)
+        VM_R(recip_dxV, 1, 0, recip_dxVe) VM_R(fCoriG, 0, 0, fCoriG) VM_R(fCoriG, 0, 1, fCoriGn)
+        VM_R(fCoriG, 1, 0, fCoriGe) VM_R(rA, 0, 0, rA) VM_R(rA, -1, 0, rAw_w) VM_R(rA, 0, -1, rA_s)
+#undef VM_R
+      }
+      return a.f.a2[(long)F * a.d.N2all + MG_I2(a.d, ii, jj, a.t)];   // anything else: where it lies
+    }
+  }
 };
 
-__global__ void __launch_bounds__(VT_NT) k_mom_vi_tiled(Dims d, Params p, Fields f, const int *iterPtr, int BX, int BY,
-                                                         int nbx, int nby, int KC, int nkc) {
-  __shared__ double sU[3 * VT_EMAX], sV[3 * VT_EMAX], sHW[3 * VT_EMAX], sHS[3 * VT_EMAX], sHC[3 * VT_EMAX];
-  __shared__ double sW[2 * VT_EMAX];
-  __shared__ double sKE[VT_IMAX], sVort[VT_IMAX], sHfz[VT_IMAX], sH0fz[VT_IMAX], sHDiv[VT_IMAX];
-  // block id: (i,j) block fastest, then the chunk of KC levels, then the tile
-  const int nb = nbx * nby, lb = mg_xcd_block();
-  const int t = d.t0 + lb / (nb * nkc), bxy = lb % nb, kb = 1 + ((lb / nb) % nkc) * KC;
-  const int ke = kb + KC - 1 < d.Nr ? kb + KC - 1 : d.Nr;
-  const int i0 = (bxy % nbx) * BX, j0 = (bxy / nbx) * BY;
-  const int tid = threadIdx.x;
-  const int EW = BX + 2, EN = (BX + 2) * (BY + 2), IW = BX + 1, IN = (BX + 1) * (BY + 1);
-  const int Nr = d.Nr;
-  const int i = i0 + tid % BX, j = j0 + tid / BX;
-  const bool act = tid < BX * BY && i <= d.sNx + 1 && j <= d.sNy + 1;
-  const int myIter = *iterPtr;
-  const double abFac = (myIter == p.nIter0 && p.nIter0 == 0) ? 0.0 : 0.5 + p.abEps;   // adams_bashforth2.F:61-65
-  const double mass2rUnit = 1.0 / p.rhoConst;
-  const bool rstar = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
-  const long q2 = MG_I2(d, i, j, t);
-  VITile a{d, p, f, 1, t, i0, j0, EW, IW, sU, sV, sW, sHW, sHS, sHC, sKE, sVort, sHfz, sH0fz, sHDiv};
-  // the block's extent: i0-1..i0+BX, j0-1..j0+BY, clipped to the array (points past it are
-  // read by no active thread)
-  auto ext_q3 = [&](int ee, int kk, bool &in) -> long {
-    const int ii = i0 - 1 + ee % EW, jj = j0 - 1 + ee / EW;
-    in = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-    return MG_I3(d, in ? ii : 1, in ? jj : 1, kk, t);
-  };
-  double nU[2], nV[2], nW[2], nHW[2], nHS[2], nHC[2];
-  auto fetch = [&](int kk) {
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-      const int ee = tid + r * VT_NT;
-      bool in = false;
-      if (ee < EN) {
-        const long q = ext_q3(ee, kk, in);
-        nU[r] = in ? AR3(uVel, q) : 0.0; nV[r] = in ? AR3(vVel, q) : 0.0; nW[r] = in ? AR3(wVel, q) : 0.0;
-        nHW[r] = in ? AR3(hFacW, q) : 0.0; nHS[r] = in ? AR3(hFacS, q) : 0.0; nHC[r] = in ? AR3(hFacC, q) : 0.0;
-      }
-    }
-  };
-  auto stash = [&](int kk) {
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-      const int ee = tid + r * VT_NT;
-      if (ee < EN) {
-        const int o = (kk % 3) * VT_EMAX + ee;
-        sU[o] = nU[r]; sV[o] = nV[r]; sHW[o] = nHW[r]; sHS[o] = nHS[r]; sHC[o] = nHC[r];
-        sW[(kk & 1) * VT_EMAX + ee] = nW[r];
-      }
-    }
-  };
-  // levels kb-1 (the vertical shear / viscous flux partner above) and kb
-  if (kb > 1) { fetch(kb - 1); stash(kb - 1); }
-  fetch(kb);
-  stash(kb);
-  __syncthreads();
-  for (int k = kb; k <= ke; k++) {
-    a.k = k;
-    if (k < Nr) fetch(k + 1);   // in flight while level k's intermediates are formed
-    // per-level intermediates on the (BX+1) x (BY+1) grids
-    for (int q = tid; q < IN; q += VT_NT) {
-      const int ii = i0 + q % IW, jj = j0 + q / IW;          // vort / hFacZ grid: i0..i0+BX
-      const bool ok = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-      sHfz[q] = ok ? vi_hfacz(a, d, ii, jj, k) : 0.0;
-      sH0fz[q] = ok ? vi_h0facz(a, d, p, ii, jj, k) : 0.0;
-      sVort[q] = ok ? vi_vort(a, d, p, f, ii, jj, k, t) : 0.0;
-      const int ih = ii - 1, jh = jj - 1;                     // KE / hDiv grid: i0-1..i0+BX-1
-      sKE[q] = vi_KE(a, d, p, f, ih, jh, k, t);
-      sHDiv[q] = vi_hdiv(a, d, p, f, ih, jh, k, t);
-    }
-    if (k < Nr) stash(k + 1);
-    __syncthreads();
-    if (act) {
-      const long q3 = MG_I3(d, i, j, k, t);
-      const double recip_drF = f.recip_drF[k - 1];
-      double gU = 0.0, gV = 0.0, guDiss = 0.0, gvDiss = 0.0, dPhiHydX = 0.0, dPhiHydY = 0.0;
-      {  // CALC_GRAD_PHI_HYD (calc_grad_phi_hyd.F:152-214), as k_mom_step
-        const bool rsc = rstar && p.select_rStar >= 2 && p.nonlinFreeSurf >= 4;
-        auto varLoc = [&](int ii, int jj) {
-          return rsc ? AR3(phiHydC, MG_I3(d, ii, jj, k, t)) * AR2(rStarFacC, MG_I2(d, ii, jj, t)) + 0.0
-                     : AR3(phiHydC, MG_I3(d, ii, jj, k, t)) + 0.0;
-        };
-        const double vl = varLoc(i, j);
-        if (i >= 1) dPhiHydX = AR2(recip_dxC, q2) * (vl - varLoc(i - 1, j));
-        if (j >= 1) dPhiHydY = AR2(recip_dyC, q2) * (vl - varLoc(i, j - 1));
-        if (rstar && p.select_rStar >= 2) {
-          const double factorP = p.gravity * (1.0 / p.rhoConst) * 0.5, rCk = f.rC[k - 1];
-          auto vl2 = [&](int ii, int jj) { return AR2(etaH, MG_I2(d, ii, jj, t)) * (1.0 + rCk * AR2(recip_Rcol, MG_I2(d, ii, jj, t))); };
-          const double e0 = vl2(i, j), a0 = AR3(alphaRho, q3);
-          if (i >= 1)
-            dPhiHydX = dPhiHydX + factorP * (AR3(alphaRho, MG_I3(d, i - 1, j, k, t)) + a0) * (e0 - vl2(i - 1, j)) * AR2(recip_dxC, q2);
-          if (j >= 1)
-            dPhiHydY = dPhiHydY + factorP * (AR3(alphaRho, MG_I3(d, i, j - 1, k, t)) + a0) * (e0 - vl2(i, j - 1)) * AR2(recip_dyC, q2);
-        }
-      }
-      vecinv_tend(a, d, p, f, i, j, k, t, gU, gV, guDiss, gvDiss);
-      // TIMESTEP (timestep.F:104-388), as k_mom_step
-      double guExt = 0.0, gvExt = 0.0;
-      if (p.momForcing && k == 1) {
-        if (j >= 0 && j <= d.sNy + 1 && i >= 1 && i <= d.sNx + 1)
-          guExt = guExt + p.foFacMom * (AR2(fu, q2) * mass2rUnit) * recip_drF * a.recip_hFacW(i, j, k);
-        if (j >= 1 && j <= d.sNy + 1 && i >= 0 && i <= d.sNx + 1)
-          gvExt = gvExt + p.foFacMom * (AR2(fv, q2) * mass2rUnit) * recip_drF * a.recip_hFacS(i, j, k);
-      }
-      gU = gU - p.pfFacMom * dPhiHydX;
-      gV = gV - p.pfFacMom * dPhiHydY;
-      if (p.momViscosity && p.momDissip_In_AB) { gU = gU + guDiss; gV = gV + gvDiss; }
-      if (p.momForcing && p.momForcingOutAB != 1) { gU = gU + guExt; gV = gV + gvExt; }
-      {  // ADAMS_BASHFORTH2 (adams_bashforth2.F:81-88)
-        const double gUo = AR3(guNm1, q3), gVo = AR3(gvNm1, q3);
-        double ab = abFac * (gU - gUo);
-        AR3(guNm1, q3) = gU;
-        gU = gU + ab;
-        ab = abFac * (gV - gVo);
-        AR3(gvNm1, q3) = gV;
-        gV = gV + ab;
-      }
-      double gUtmp = gU, gVtmp = gV;
-      if (p.momForcing && p.momForcingOutAB == 1) { gUtmp = gUtmp + guExt; gVtmp = gVtmp + gvExt; }
-      if (p.momViscosity && !p.momDissip_In_AB) { gUtmp = gUtmp + guDiss; gVtmp = gVtmp + gvDiss; }
-      if (rstar && p.nonlinFreeSurf > 1) {
-        gUtmp = gUtmp / AR2(rStarExpW, q2);
-        gVtmp = gVtmp / AR2(rStarExpS, q2);
-      }
-      AR3(gU, q3) = a.uVel(i, j, k) + p.deltaTMom * (gUtmp + 0.0) * a.maskW(i, j, k);
-      AR3(gV, q3) = a.vVel(i, j, k) + p.deltaTMom * (gVtmp + 0.0) * a.maskS(i, j, k);
-    }
-    __syncthreads();
+// The ring-point intermediates of level ai.k on the block's (BX+1) x (BY+1) grids (IN points,
+// IW = BX+1 wide), into the accessor's LDS arrays
+template <class A, class P>
+__device__ __forceinline__ void vi_intermediates(const A &ai, const Dims &d, const P &p, const Fields &f, int tid, int IN) {
+  const int k = ai.k, t = ai.t;
+  for (int q = tid; q < IN; q += VT_NT) {
+    const int ii = ai.i0 + q % ai.IW, jj = ai.j0 + q / ai.IW;          // vort / hFacZ grid: i0..i0+BX
+    const bool ok = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
+    ai.sHfz[q] = ok ? vi_hfacz(ai, d, ii, jj, k) : 0.0;
+    ai.sH0fz[q] = ok ? vi_h0facz(ai, d, p, ii, jj, k) : 0.0;
+    ai.sVort[q] = ok ? vi_vort(ai, d, p, f, ii, jj, k, t) : 0.0;
+    ai.sKE[q] = vi_KE(ai, d, p, f, ii - 1, jj - 1, k, t);     // KE / hDiv grid: i0-1..i0+BX-1
+    ai.sHDiv[q] = vi_hdiv(ai, d, p, f, ii - 1, jj - 1, k, t);
   }
 }
 
-// One level per workgroup: level k of the block plus one ring staged in LDS (u, v, w,
-// hFacW, hFacS, hFacC), the intermediates formed once per point into LDS; the other
-// levels' values (vertical shear, vertical viscous fluxes, masks at k-1 / k+1, w(k+1))
-// are read where they lie.  No level march: many small workgroups, modest registers.
-struct VILevel {
-  const Dims &d; const Params &p; const Fields &f; int k, t, i0, j0, EW, IW;
-  const double *sU, *sV, *sW, *sHW, *sHS, *sHC;   // level k on the extent
-  const double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
-  __device__ __forceinline__ int e(int ii, int jj) const { return (jj - j0 + 1) * EW + (ii - i0 + 1); }
-  __device__ __forceinline__ long g(int ii, int jj, int kk) const { return MG_I3(d, ii, jj, kk, t); }
-  template <int F> __device__ __forceinline__ double g2(int ii, int jj) const { return f.a2[(long)F * d.N2all + MG_I2(d, ii, jj, t)]; }
-  __device__ __forceinline__ double uVel(int ii, int jj, int kk) const { return kk == k ? sU[e(ii, jj)] : AR3(uVel, g(ii, jj, kk)); }
-  __device__ __forceinline__ double vVel(int ii, int jj, int kk) const { return kk == k ? sV[e(ii, jj)] : AR3(vVel, g(ii, jj, kk)); }
-  __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return kk == k ? sW[e(ii, jj)] : AR3(wVel, g(ii, jj, kk)); }
-  __device__ __forceinline__ double hFacW(int ii, int jj, int kk) const { return kk == k ? sHW[e(ii, jj)] : AR3(hFacW, g(ii, jj, kk)); }
-  __device__ __forceinline__ double hFacS(int ii, int jj, int kk) const { return kk == k ? sHS[e(ii, jj)] : AR3(hFacS, g(ii, jj, kk)); }
-  __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return kk == k ? sHC[e(ii, jj)] : AR3(hFacC, g(ii, jj, kk)); }
-  __device__ __forceinline__ double maskW(int ii, int jj, int kk) const { return hFacW(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskS(int ii, int jj, int kk) const { return hFacS(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskC(int ii, int jj, int kk) const { return hFacC(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double recip_hFacW(int ii, int jj, int kk) const {
-    const double h = hFacW(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacS(int ii, int jj, int kk) const {
-    const double h = hFacS(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacC(int ii, int jj, int kk) const {
-    const double h = hFacC(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double h0FacW(int ii, int jj, int kk) const { return AR3(h0FacW, g(ii, jj, kk)); }
-  __device__ __forceinline__ double h0FacS(int ii, int jj, int kk) const { return AR3(h0FacS, g(ii, jj, kk)); }
-  __device__ __forceinline__ int iv(int ii, int jj) const { return (jj - j0) * IW + (ii - i0); }
-  __device__ __forceinline__ int id(int ii, int jj) const { return (jj - j0 + 1) * IW + (ii - i0 + 1); }
-  __device__ __forceinline__ double hfz(int ii, int jj) const { return sHfz[iv(ii, jj)]; }
-  __device__ __forceinline__ double h0fz(int ii, int jj) const { return sH0fz[iv(ii, jj)]; }
-  __device__ __forceinline__ double vort(int ii, int jj) const { return sVort[iv(ii, jj)]; }
-  __device__ __forceinline__ double KE(int ii, int jj) const { return sKE[id(ii, jj)]; }
-  __device__ __forceinline__ double hDiv(int ii, int jj) const { return sHDiv[id(ii, jj)]; }
-};
-
-__global__ void __launch_bounds__(VT_NT) k_mom_vi_level(Dims d, Params p, Fields f, const int *iterPtr, int BX, int BY,
-                                                         int nbx, int nby) {
-  __shared__ double sU[VT_EMAX], sV[VT_EMAX], sW[VT_EMAX], sHW[VT_EMAX], sHS[VT_EMAX], sHC[VT_EMAX];
-  __shared__ double sKE[VT_IMAX], sVort[VT_IMAX], sHfz[VT_IMAX], sH0fz[VT_IMAX], sHDiv[VT_IMAX];
-  // block id: (i,j) block fastest, then the level, then the tile
-  const int nb = nbx * nby, lb = mg_xcd_block();
-  const int t = d.t0 + lb / (nb * d.Nr), bxy = lb % nb, k = 1 + (lb / nb) % d.Nr;
-  const int i0 = (bxy % nbx) * BX, j0 = (bxy / nbx) * BY;
-  const int tid = threadIdx.x;
-  const int EW = BX + 2, EN = (BX + 2) * (BY + 2), IW = BX + 1, IN = (BX + 1) * (BY + 1);
-  const int i = i0 + tid % BX, j = j0 + tid / BX;
-  const bool act = tid < BX * BY && i <= d.sNx + 1 && j <= d.sNy + 1;
-  VILevel a{d, p, f, k, t, i0, j0, EW, IW, sU, sV, sW, sHW, sHS, sHC, sKE, sVort, sHfz, sH0fz, sHDiv};
-  for (int ee = tid; ee < EN; ee += VT_NT) {
-    const int ii = i0 - 1 + ee % EW, jj = j0 - 1 + ee / EW;
-    const bool in = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-    const long q = MG_I3(d, in ? ii : 1, in ? jj : 1, k, t);
-    sU[ee] = in ? AR3(uVel, q) : 0.0; sV[ee] = in ? AR3(vVel, q) : 0.0; sW[ee] = in ? AR3(wVel, q) : 0.0;
-    sHW[ee] = in ? AR3(hFacW, q) : 0.0; sHS[ee] = in ? AR3(hFacS, q) : 0.0; sHC[ee] = in ? AR3(hFacC, q) : 0.0;
-  }
-  __syncthreads();
-  for (int q = tid; q < IN; q += VT_NT) {
-    const int ii = i0 + q % IW, jj = j0 + q / IW;
-    const bool ok = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-    sHfz[q] = ok ? vi_hfacz(a, d, ii, jj, k) : 0.0;
-    sH0fz[q] = ok ? vi_h0facz(a, d, p, ii, jj, k) : 0.0;
-    sVort[q] = ok ? vi_vort(a, d, p, f, ii, jj, k, t) : 0.0;
-    sKE[q] = vi_KE(a, d, p, f, ii - 1, jj - 1, k, t);
-    sHDiv[q] = vi_hdiv(a, d, p, f, ii - 1, jj - 1, k, t);
-  }
-  __syncthreads();
-  if (!act) return;
-  const int myIter = *iterPtr;
-  const double abFac = (myIter == p.nIter0 && p.nIter0 == 0) ? 0.0 : 0.5 + p.abEps;   // adams_bashforth2.F:61-65
-  const double mass2rUnit = 1.0 / p.rhoConst;
+// The output point (i, j, k) after the intermediates: CALC_GRAD_PHI_HYD
+// (calc_grad_phi_hyd.F:152-214), vecinv_tend, TIMESTEP's forcing (timestep.F:104-388),
+// ADAMS_BASHFORTH2 (adams_bashforth2.F:81-88), the r* rescale and the gU / gV store, as
+// k_mom_step, for the level kernel and the generic march.  q2 / q3: the point's flat 2-D / 3-D
+// offsets.  (k_mom_vi_m2 keeps the same arithmetic in its per-component form.)
+template <class A, class P>
+__device__ __forceinline__ void vi_point_tail(const A &a, const Dims &d, const P &p, const Fields &f, int i, int j, int k,
+                                              int t, long q2, long q3, double recip_drF, double abFac, double mass2rUnit) {
   const bool rstar = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
-  const long q2 = MG_I2(d, i, j, t), q3 = MG_I3(d, i, j, k, t);
-  const double recip_drF = f.recip_drF[k - 1];
   double gU = 0.0, gV = 0.0, guDiss = 0.0, gvDiss = 0.0, dPhiHydX = 0.0, dPhiHydY = 0.0;
-  {  // CALC_GRAD_PHI_HYD (calc_grad_phi_hyd.F:152-214), as k_mom_step
+  {  // CALC_GRAD_PHI_HYD
     const bool rsc = rstar && p.select_rStar >= 2 && p.nonlinFreeSurf >= 4;
-    auto varLoc = [&](int ii, int jj) {
-      return rsc ? AR3(phiHydC, MG_I3(d, ii, jj, k, t)) * AR2(rStarFacC, MG_I2(d, ii, jj, t)) + 0.0
-                 : AR3(phiHydC, MG_I3(d, ii, jj, k, t)) + 0.0;
+    auto varLoc = [&](long o) {
+      return rsc ? AR3(phiHydC, q3 - o) * AR2(rStarFacC, q2 - o) + 0.0 : AR3(phiHydC, q3 - o) + 0.0;
     };
-    const double vl = varLoc(i, j);
-    if (i >= 1) dPhiHydX = AR2(recip_dxC, q2) * (vl - varLoc(i - 1, j));
-    if (j >= 1) dPhiHydY = AR2(recip_dyC, q2) * (vl - varLoc(i, j - 1));
+    const double vl = varLoc(0);
+    if (i >= 1) dPhiHydX = a.template g2<F2_recip_dxC>(i, j) * (vl - varLoc(1));
+    if (j >= 1) dPhiHydY = a.template g2<F2_recip_dyC>(i, j) * (vl - varLoc(d.nx));
     if (rstar && p.select_rStar >= 2) {
       const double factorP = p.gravity * (1.0 / p.rhoConst) * 0.5, rCk = f.rC[k - 1];
-      auto vl2 = [&](int ii, int jj) { return AR2(etaH, MG_I2(d, ii, jj, t)) * (1.0 + rCk * AR2(recip_Rcol, MG_I2(d, ii, jj, t))); };
-      const double e0 = vl2(i, j), a0 = AR3(alphaRho, q3);
+      auto vl2 = [&](long qq2) { return AR2(etaH, qq2) * (1.0 + rCk * AR2(recip_Rcol, qq2)); };
+      const double e0 = vl2(q2), a0 = AR3(alphaRho, q3);
       if (i >= 1)
-        dPhiHydX = dPhiHydX + factorP * (AR3(alphaRho, MG_I3(d, i - 1, j, k, t)) + a0) * (e0 - vl2(i - 1, j)) * AR2(recip_dxC, q2);
+        dPhiHydX = dPhiHydX + factorP * (AR3(alphaRho, q3 - 1) + a0) * (e0 - vl2(q2 - 1)) * a.template g2<F2_recip_dxC>(i, j);
       if (j >= 1)
-        dPhiHydY = dPhiHydY + factorP * (AR3(alphaRho, MG_I3(d, i, j - 1, k, t)) + a0) * (e0 - vl2(i, j - 1)) * AR2(recip_dyC, q2);
+        dPhiHydY = dPhiHydY + factorP * (AR3(alphaRho, q3 - d.nx) + a0) * (e0 - vl2(q2 - d.nx)) * a.template g2<F2_recip_dyC>(i, j);
     }
   }
   vecinv_tend(a, d, p, f, i, j, k, t, gU, gV, guDiss, gvDiss);
@@ -1555,7 +1408,7 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_level(Dims d, Params p, Fields
   gV = gV - p.pfFacMom * dPhiHydY;
   if (p.momViscosity && p.momDissip_In_AB) { gU = gU + guDiss; gV = gV + gvDiss; }
   if (p.momForcing && p.momForcingOutAB != 1) { gU = gU + guExt; gV = gV + gvExt; }
-  {
+  {  // ADAMS_BASHFORTH2
     const double gUo = AR3(guNm1, q3), gVo = AR3(gvNm1, q3);
     double ab = abFac * (gU - gUo);
     AR3(guNm1, q3) = gU;
@@ -1575,6 +1428,55 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_level(Dims d, Params p, Fields
   AR3(gV, q3) = a.vVel(i, j, k) + p.deltaTMom * (gVtmp + 0.0) * a.maskS(i, j, k);
 }
 
+// One level per workgroup: level k of the block plus one ring staged in LDS (u, v, w,
+// hFacW, hFacS, hFacC), the intermediates formed once per point into LDS; the other
+// levels' values (vertical shear, vertical viscous fluxes, masks at k-1 / k+1, w(k+1))
+// are read where they lie.  No level march: many small workgroups, modest registers.
+struct VILevel : VIStaged<VILevel> {
+  const Dims &d; const Params &p; const Fields &f; int k, t, i0, j0, EW, IW;
+  const double *sU, *sV, *sW, *sHW, *sHS, *sHC;   // level k on the extent
+  double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
+  __device__ __forceinline__ int e(int ii, int jj) const { return (jj - j0 + 1) * EW + (ii - i0 + 1); }
+  __device__ __forceinline__ long g(int ii, int jj, int kk) const { return MG_I3(d, ii, jj, kk, t); }
+  template <int F> __device__ __forceinline__ double g2(int ii, int jj) const { return f.a2[(long)F * d.N2all + MG_I2(d, ii, jj, t)]; }
+  __device__ __forceinline__ double uVel(int ii, int jj, int kk) const { return kk == k ? sU[e(ii, jj)] : AR3(uVel, g(ii, jj, kk)); }
+  __device__ __forceinline__ double vVel(int ii, int jj, int kk) const { return kk == k ? sV[e(ii, jj)] : AR3(vVel, g(ii, jj, kk)); }
+  __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return kk == k ? sW[e(ii, jj)] : AR3(wVel, g(ii, jj, kk)); }
+  __device__ __forceinline__ double hFacW(int ii, int jj, int kk) const { return kk == k ? sHW[e(ii, jj)] : AR3(hFacW, g(ii, jj, kk)); }
+  __device__ __forceinline__ double hFacS(int ii, int jj, int kk) const { return kk == k ? sHS[e(ii, jj)] : AR3(hFacS, g(ii, jj, kk)); }
+  __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return kk == k ? sHC[e(ii, jj)] : AR3(hFacC, g(ii, jj, kk)); }
+};
+
+__global__ void __launch_bounds__(VT_NT) k_mom_vi_level(Dims d, Params p, Fields f, const int *iterPtr, int BX, int BY,
+                                                         int nbx, int nby) {
+  __shared__ double sU[VT_EMAX], sV[VT_EMAX], sW[VT_EMAX], sHW[VT_EMAX], sHS[VT_EMAX], sHC[VT_EMAX];
+  __shared__ double sKE[VT_IMAX], sVort[VT_IMAX], sHfz[VT_IMAX], sH0fz[VT_IMAX], sHDiv[VT_IMAX];
+  // block id: (i,j) block fastest, then the level, then the tile
+  const int nb = nbx * nby, lb = mg_xcd_block();
+  const int t = d.t0 + lb / (nb * d.Nr), bxy = lb % nb, k = 1 + (lb / nb) % d.Nr;
+  const int i0 = (bxy % nbx) * BX, j0 = (bxy / nbx) * BY;
+  const int tid = threadIdx.x;
+  const int EW = BX + 2, EN = (BX + 2) * (BY + 2), IW = BX + 1, IN = (BX + 1) * (BY + 1);
+  const int i = i0 + tid % BX, j = j0 + tid / BX;
+  const bool act = tid < BX * BY && i <= d.sNx + 1 && j <= d.sNy + 1;
+  VILevel a{{}, d, p, f, k, t, i0, j0, EW, IW, sU, sV, sW, sHW, sHS, sHC, sKE, sVort, sHfz, sH0fz, sHDiv};
+  for (int ee = tid; ee < EN; ee += VT_NT) {
+    const int ii = i0 - 1 + ee % EW, jj = j0 - 1 + ee / EW;
+    const bool in = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
+    const long q = MG_I3(d, in ? ii : 1, in ? jj : 1, k, t);
+    sU[ee] = in ? AR3(uVel, q) : 0.0; sV[ee] = in ? AR3(vVel, q) : 0.0; sW[ee] = in ? AR3(wVel, q) : 0.0;
+    sHW[ee] = in ? AR3(hFacW, q) : 0.0; sHS[ee] = in ? AR3(hFacS, q) : 0.0; sHC[ee] = in ? AR3(hFacC, q) : 0.0;
+  }
+  __syncthreads();
+  vi_intermediates(a, d, p, f, tid, IN);
+  __syncthreads();
+  if (!act) return;
+  const int myIter = *iterPtr;
+  const double abFac = (myIter == p.nIter0 && p.nIter0 == 0) ? 0.0 : 0.5 + p.abEps;   // adams_bashforth2.F:61-65
+  vi_point_tail(a, d, p, f, i, j, k, t, MG_I2(d, i, j, t), MG_I3(d, i, j, k, t), f.recip_drF[k - 1], abFac,
+                   1.0 / p.rhoConst);
+}
+
 // ---------------------------------------------------------------------------------------
 // MOM_VECINV + CALC_GRAD_PHI_HYD + TIMESTEP + ADAMS_BASHFORTH2 as a register-pipelined
 // k-march (default for VI): a workgroup owns a BX x BY block of the DYNAMICS range of one
@@ -1586,20 +1488,14 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_level(Dims d, Params p, Fields
 // u, v, hFacW, hFacS over the extent, hFacC in a 2-slot ring (maskC at k-1) and w in a
 // 2-slot ring (w at k+1); the vertical neighbours the output point needs (u, v, hFacW,
 // hFacS at k-1 and k+1) are its own column's values, carried in registers.  Level k+1
-// (and w at k+2) is fetched into registers while level k is computed, every load
+// (and w at k+2) is fetched into registers after level k's output, every load
 // unconditional with clamped indices, so a level's loads issue together.  The expression
 // trees are vecinv_tend's (accessor VIMarch), so the result is bit-identical to the
 // per-point and per-level kernels.
-struct VIMarchRegs {   // the output point's own 2-D values (i,j); n = (i,j+1), e = (i+1,j), w = (i-1,j), s = (i,j-1)
-  double recip_dxC, recip_dyC, recip_dxG, recip_dyG, rAw, rAs, recip_rAw, recip_rAs;
-  double dxV, dxVn, recip_dyU, recip_dyUn, dyU, dyUe, recip_dxV, recip_dxVe;
-  double fCoriG, fCoriGn, fCoriGe, rA, rAw_w, rA_s;
-};
-constexpr int VM_S2 = 6;   // LDS-staged 2-D fields: dxC, dyC, recip_rAz, dxG, dyG, recip_rA
-struct VIMarch {
+struct VIMarch : VIStaged<VIMarch> {
   const Dims &d; const Params &p; const Fields &f; int k, t, i0, j0, EW, IW, i, j;
   const double *sU, *sV, *sHW, *sHS, *sHC, *sW, *s2;
-  const double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
+  double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
   const VIMarchRegs &c;
   double uM, uP, vM, vP, hwM, hwP, hsM, hsP;   // own column at k-1 and k+1
   __device__ __forceinline__ int e(int ii, int jj) const { return (jj - j0 + 1) * EW + (ii - i0 + 1); }
@@ -1618,49 +1514,12 @@ struct VIMarch {
   __device__ __forceinline__ double hFacS(int ii, int jj, int kk) const { return lvl(sHS, hsM, hsP, ii, jj, kk); }
   __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return sHC[(kk & 1) * VT_EMAX + e(ii, jj)]; }
   __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return sW[(kk & 1) * VT_EMAX + e(ii, jj)]; }
-  __device__ __forceinline__ double maskW(int ii, int jj, int kk) const { return hFacW(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskS(int ii, int jj, int kk) const { return hFacS(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskC(int ii, int jj, int kk) const { return hFacC(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double recip_hFacW(int ii, int jj, int kk) const {
-    const double h = hFacW(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacS(int ii, int jj, int kk) const {
-    const double h = hFacS(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacC(int ii, int jj, int kk) const {
-    const double h = hFacC(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double h0FacW(int ii, int jj, int kk) const { return AR3(h0FacW, g(ii, jj, kk)); }
-  __device__ __forceinline__ double h0FacS(int ii, int jj, int kk) const { return AR3(h0FacS, g(ii, jj, kk)); }
-  template <int F> __device__ __forceinline__ double g2(int ii, int jj) const {
-    const int di = ii - i, dj = jj - j;
-    if constexpr (F == F2_dxC) return s2[0 * VT_EMAX + e(ii, jj)];
-    else if constexpr (F == F2_dyC) return s2[1 * VT_EMAX + e(ii, jj)];
-    else if constexpr (F == F2_recip_rAz) return s2[2 * VT_EMAX + e(ii, jj)];
-    else if constexpr (F == F2_dxG) return s2[3 * VT_EMAX + e(ii, jj)];
-    else if constexpr (F == F2_dyG) return s2[4 * VT_EMAX + e(ii, jj)];
-    else if constexpr (F == F2_recip_rA) return s2[5 * VT_EMAX + e(ii, jj)];
-    else {
-#define VM_R(name, DI, DJ, reg) if constexpr (F == F2_##name) { if (di == (DI) && dj == (DJ)) return c.reg; }
-      VM_R(recip_dxC, 0, 0, recip_dxC) VM_R(recip_dyC, 0, 0, recip_dyC) VM_R(recip_dxG, 0, 0, recip_dxG)
-      VM_R(recip_dyG, 0, 0, recip_dyG) VM_R(rAw, 0, 0, rAw) VM_R(rAs, 0, 0, rAs) VM_R(recip_rAw, 0, 0, recip_rAw)
-      VM_R(recip_rAs, 0, 0, recip_rAs) VM_R(dxV, 0, 0, dxV) VM_R(dxV, 0, 1, dxVn) VM_R(recip_dyU, 0, 0, recip_dyU)
-      VM_R(recip_dyU, 0, 1, recip_dyUn) VM_R(dyU, 0, 0, dyU) VM_R(dyU, 1, 0, dyUe) VM_R(recip_dxV, 0, 0, recip_dxV)
-      VM_R(recip_dxV, 1, 0, recip_dxVe) VM_R(fCoriG, 0, 0, fCoriG) VM_R(fCoriG, 0, 1, fCoriGn)
-      VM_R(fCoriG, 1, 0, fCoriGe) VM_R(rA, 0, 0, rA) VM_R(rA, -1, 0, rAw_w) VM_R(rA, 0, -1, rA_s)
-#undef VM_R
-      return f.a2[(long)F * d.N2all + MG_I2(d, ii, jj, t)];   // anything else: where it lies
-    }
-  }
-  __device__ __forceinline__ int iv(int ii, int jj) const { return (jj - j0) * IW + (ii - i0); }
-  __device__ __forceinline__ int id(int ii, int jj) const { return (jj - j0 + 1) * IW + (ii - i0 + 1); }
-  __device__ __forceinline__ double hfz(int ii, int jj) const { return sHfz[iv(ii, jj)]; }
-  __device__ __forceinline__ double h0fz(int ii, int jj) const { return sH0fz[iv(ii, jj)]; }
-  __device__ __forceinline__ double vort(int ii, int jj) const { return sVort[iv(ii, jj)]; }
-  __device__ __forceinline__ double KE(int ii, int jj) const { return sKE[id(ii, jj)]; }
-  __device__ __forceinline__ double hDiv(int ii, int jj) const { return sHDiv[id(ii, jj)]; }
+  template <int F> __device__ __forceinline__ double g2(int ii, int jj) const { return g2_march<F, true>(VT_EMAX, ii, jj); }
 };
 
-// PF: fetch level k+1 into registers during level k (else after it); CREG: the output
-// point's metrics held in registers across the march (else re-read every level)
-template <bool PF, bool CREG>
+// (Fetching level k+1 during level k, and holding the output point's metrics in registers
+// across the march instead of re-reading them every level, were never launched in this
+// kernel; vi_m2_launch has what they measured in k_mom_vi_m2.)
 __global__ void __launch_bounds__(VT_NT) k_mom_vi_march(Dims d, Params p, Fields f, const int *iterPtr, int BX, int BY,
                                                          int nbx, int nby, int KC, int nkc) {
   __shared__ double sU[VT_EMAX], sV[VT_EMAX], sHW[VT_EMAX], sHS[VT_EMAX], sHC[2 * VT_EMAX], sW[2 * VT_EMAX];
@@ -1700,18 +1559,6 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_march(Dims d, Params p, Fields
         if (ee < EN) s2[n * VT_EMAX + ee] = ein[r] ? v : 0.0;
       }
   }
-  auto load_c = [&](VIMarchRegs &c, const long q2) {
-    const long qn = q2 + d.nx, qe = q2 + 1, qw = q2 - 1, qs = q2 - d.nx;
-    c.recip_dxC = AR2(recip_dxC, q2); c.recip_dyC = AR2(recip_dyC, q2);
-    c.recip_dxG = AR2(recip_dxG, q2); c.recip_dyG = AR2(recip_dyG, q2);
-    c.rAw = AR2(rAw, q2); c.rAs = AR2(rAs, q2); c.recip_rAw = AR2(recip_rAw, q2); c.recip_rAs = AR2(recip_rAs, q2);
-    c.dxV = AR2(dxV, q2); c.dxVn = AR2(dxV, qn); c.recip_dyU = AR2(recip_dyU, q2); c.recip_dyUn = AR2(recip_dyU, qn);
-    c.dyU = AR2(dyU, q2); c.dyUe = AR2(dyU, qe); c.recip_dxV = AR2(recip_dxV, q2); c.recip_dxVe = AR2(recip_dxV, qe);
-    c.fCoriG = AR2(fCoriG, q2); c.fCoriGn = AR2(fCoriG, qn); c.fCoriGe = AR2(fCoriG, qe);
-    c.rA = AR2(rA, q2); c.rAw_w = AR2(rA, qw); c.rA_s = AR2(rA, qs);
-  };
-  VIMarchRegs c0;   // CREG: loaded once, live in registers across the march
-  if constexpr (CREG) load_c(c0, q2);
   // level fetches into registers (unconditional loads, masked where the element is absent),
   // addressed as uniform field base + 32-bit byte offset (the global_load saddr form)
   const long t3 = (long)t * (d.n3 - d.n2);   // MG_I3 = MG_I2 + (k-1)*n2 + t*(n3-n2)
@@ -1777,8 +1624,6 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_march(Dims d, Params p, Fields
   stash(kb);
   const int myIter = *iterPtr;
   const double abFac = (myIter == p.nIter0 && p.nIter0 == 0) ? 0.0 : 0.5 + p.abEps;   // adams_bashforth2.F:61-65
-  const double mass2rUnit = 1.0 / p.rhoConst;
-  const bool rstar = p.nonlinFreeSurf > 0 && p.select_rStar > 0;
   __syncthreads();
   for (int k = kb; k <= ke; k++) {
     // the thread's coordinates re-materialised each level (an empty asm the compiler cannot
@@ -1788,93 +1633,29 @@ __global__ void __launch_bounds__(VT_NT) k_mom_vi_march(Dims d, Params p, Fields
     long q2L = q2;
     asm volatile("" : "+v"(iL), "+v"(jL), "+v"(q2L));
     [&](const int i, const int j, const long q2) {
-    VIMarchRegs c1;   // !CREG: re-read every level (cache hits) instead of held across the march
-    if constexpr (!CREG) load_c(c1, q2);
-    const VIMarchRegs &c = CREG ? c0 : c1;
-    const int kn = k + 1 <= Nr ? k + 1 : Nr, kw = k + 2 <= Nr ? k + 2 : Nr;
-    if constexpr (PF) {
-      fetch(kn);    // level k+1 and the own column at k+1, in flight during level k
-      fetchW(kw);
-    } else {   // own column at k+1 only; the level itself is fetched after the output
-      const unsigned o = ob + (unsigned)(kn - 1) * lvB;
+    VIMarchRegs c;   // re-read every level (cache hits) instead of held across the march
+    c.load(d, f, q2);
+    {   // own column at k+1; the level itself is fetched after the output
+      const unsigned o = ob + (unsigned)((k + 1 <= Nr ? k + 1 : Nr) - 1) * lvB;
       oU = ld(bU, o); oV = ld(bV, o); oHW = ld(bHW, o); oHS = ld(bHS, o);
     }
     // the output point's accessor, and one for the ring-point intermediates whose own point
     // matches nothing (they read level k only; an idle thread's registers hold (1,1)'s values)
-    VIMarch a{d, p, f, k, t, i0, j0, EW, IW, i, j, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
+    VIMarch a{{}, d, p, f, k, t, i0, j0, EW, IW, i, j, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
               uM, k < Nr ? oU : 0.0, vM, k < Nr ? oV : 0.0, hwM, k < Nr ? oHW : 0.0, hsM, k < Nr ? oHS : 0.0};
-    VIMarch ai{d, p, f, k, t, i0, j0, EW, IW, -1000000, -1000000, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz,
+    VIMarch ai{{}, d, p, f, k, t, i0, j0, EW, IW, -1000000, -1000000, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz,
                sHDiv, c, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int q = tid; q < IN; q += VT_NT) {
-      const int ii = i0 + q % IW, jj = j0 + q / IW;          // vort / hFacZ grid: i0..i0+BX
-      const bool ok = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-      sHfz[q] = ok ? vi_hfacz(ai, d, ii, jj, k) : 0.0;
-      sH0fz[q] = ok ? vi_h0facz(ai, d, p, ii, jj, k) : 0.0;
-      sVort[q] = ok ? vi_vort(ai, d, p, f, ii, jj, k, t) : 0.0;
-      sKE[q] = vi_KE(ai, d, p, f, ii - 1, jj - 1, k, t);     // KE / hDiv grid: i0-1..i0+BX-1
-      sHDiv[q] = vi_hdiv(ai, d, p, f, ii - 1, jj - 1, k, t);
-    }
+    vi_intermediates(ai, d, p, f, tid, IN);
     __syncthreads();
-    if (act) {
-      auto q3of = [&](long qq2, int kk) { return qq2 + (long)(kk - 1) * d.n2 + t3; };
-      const long q3 = q3of(q2, k);
-      const double recip_drF = f.recip_drF[k - 1];
-      double gU = 0.0, gV = 0.0, guDiss = 0.0, gvDiss = 0.0, dPhiHydX = 0.0, dPhiHydY = 0.0;
-      {  // CALC_GRAD_PHI_HYD (calc_grad_phi_hyd.F:152-214), as k_mom_step
-        const bool rsc = rstar && p.select_rStar >= 2 && p.nonlinFreeSurf >= 4;
-        auto varLoc = [&](long qq2) {
-          return rsc ? AR3(phiHydC, q3of(qq2, k)) * AR2(rStarFacC, qq2) + 0.0 : AR3(phiHydC, q3of(qq2, k)) + 0.0;
-        };
-        const double vl = varLoc(q2);
-        if (i >= 1) dPhiHydX = c.recip_dxC * (vl - varLoc(q2 - 1));
-        if (j >= 1) dPhiHydY = c.recip_dyC * (vl - varLoc(q2 - d.nx));
-        if (rstar && p.select_rStar >= 2) {
-          const double factorP = p.gravity * (1.0 / p.rhoConst) * 0.5, rCk = f.rC[k - 1];
-          auto vl2 = [&](long qq2) { return AR2(etaH, qq2) * (1.0 + rCk * AR2(recip_Rcol, qq2)); };
-          const double e0 = vl2(q2), a0 = AR3(alphaRho, q3);
-          if (i >= 1) dPhiHydX = dPhiHydX + factorP * (AR3(alphaRho, q3 - 1) + a0) * (e0 - vl2(q2 - 1)) * c.recip_dxC;
-          if (j >= 1) dPhiHydY = dPhiHydY + factorP * (AR3(alphaRho, q3 - d.nx) + a0) * (e0 - vl2(q2 - d.nx)) * c.recip_dyC;
-        }
-      }
-      vecinv_tend(a, d, p, f, i, j, k, t, gU, gV, guDiss, gvDiss);
-      double guExt = 0.0, gvExt = 0.0;
-      if (p.momForcing && k == 1) {
-        if (j >= 0 && j <= d.sNy + 1 && i >= 1 && i <= d.sNx + 1)
-          guExt = guExt + p.foFacMom * (AR2(fu, q2) * mass2rUnit) * recip_drF * a.recip_hFacW(i, j, k);
-        if (j >= 1 && j <= d.sNy + 1 && i >= 0 && i <= d.sNx + 1)
-          gvExt = gvExt + p.foFacMom * (AR2(fv, q2) * mass2rUnit) * recip_drF * a.recip_hFacS(i, j, k);
-      }
-      gU = gU - p.pfFacMom * dPhiHydX;
-      gV = gV - p.pfFacMom * dPhiHydY;
-      if (p.momViscosity && p.momDissip_In_AB) { gU = gU + guDiss; gV = gV + gvDiss; }
-      if (p.momForcing && p.momForcingOutAB != 1) { gU = gU + guExt; gV = gV + gvExt; }
-      {  // ADAMS_BASHFORTH2 (adams_bashforth2.F:81-88)
-        const double gUo = AR3(guNm1, q3), gVo = AR3(gvNm1, q3);
-        double ab = abFac * (gU - gUo);
-        AR3(guNm1, q3) = gU;
-        gU = gU + ab;
-        ab = abFac * (gV - gVo);
-        AR3(gvNm1, q3) = gV;
-        gV = gV + ab;
-      }
-      double gUtmp = gU, gVtmp = gV;
-      if (p.momForcing && p.momForcingOutAB == 1) { gUtmp = gUtmp + guExt; gVtmp = gVtmp + gvExt; }
-      if (p.momViscosity && !p.momDissip_In_AB) { gUtmp = gUtmp + guDiss; gVtmp = gVtmp + gvDiss; }
-      if (rstar && p.nonlinFreeSurf > 1) {
-        gUtmp = gUtmp / AR2(rStarExpW, q2);
-        gVtmp = gVtmp / AR2(rStarExpS, q2);
-      }
-      AR3(gU, q3) = a.uVel(i, j, k) + p.deltaTMom * (gUtmp + 0.0) * a.maskW(i, j, k);
-      AR3(gV, q3) = a.vVel(i, j, k) + p.deltaTMom * (gVtmp + 0.0) * a.maskS(i, j, k);
-    }
+    if (act)
+      vi_point_tail(a, d, p, f, i, j, k, t, q2, q2 + (long)(k - 1) * d.n2 + t3, f.recip_drF[k - 1], abFac,
+                       1.0 / p.rhoConst);
     }(iL, jL, q2L);
     if (k == ke) break;
     // the own column moves down: level k becomes k-1 (read before level k+1 overwrites it)
     if (act) { const int eo = (j - j0 + 1) * EW + (i - i0 + 1); uM = sU[eo]; vM = sV[eo]; hwM = sHW[eo]; hsM = sHS[eo]; }
-    if constexpr (!PF) {
-      fetch(k + 1 <= Nr ? k + 1 : Nr);
-      fetchW(k + 2 <= Nr ? k + 2 : Nr);
-    }
+    fetch(k + 1 <= Nr ? k + 1 : Nr);
+    fetchW(k + 2 <= Nr ? k + 2 : Nr);
     __syncthreads();
     stash(k + 1);
     stashW(k + 2);
@@ -1929,12 +1710,12 @@ static VIP<C> vi_params(const Params &p) {
 // Accessor of k_mom_vi_m2.  OWN: the output point (i,j), whose column's k-1 / k+1 values of
 // u, v, hFacW, hFacS sit in registers and whose own 2-D metrics in VIMarchRegs; !OWN: the
 // ring-point intermediates, which read level k only (no own-point selects at all).
-template <int BX, int BY, class P, bool OWN, int HR = 2>
-struct VIM2 {   // HR: slots of the hFacC / wVel level rings (level kk in slot kk % HR)
+template <int BX, int BY, class P, bool OWN>
+struct VIM2 : VIStaged<VIM2<BX, BY, P, OWN>> {
   static constexpr int EW = BX + 2, IW = BX + 1;
   const Dims &d; const P &p; const Fields &f; int k, t, i0, j0, i, j;
   const double *sU, *sV, *sHW, *sHS, *sHC, *sW, *s2;
-  const double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
+  double *sKE, *sVort, *sHfz, *sH0fz, *sHDiv;
   const VIMarchRegs &c;
   double uM, uP, vM, vP, hwM, hwP, hsM, hsP;
   // filled at the level's start (vi_tile_face ... overloads below): the tile's face / edge
@@ -1953,72 +1734,34 @@ struct VIM2 {   // HR: slots of the hFacC / wVel level rings (level kk in slot k
   __device__ __forceinline__ double vVel(int ii, int jj, int kk) const { return lvl(sV, vM, vP, ii, jj, kk); }
   __device__ __forceinline__ double hFacW(int ii, int jj, int kk) const { return lvl(sHW, hwM, hwP, ii, jj, kk); }
   __device__ __forceinline__ double hFacS(int ii, int jj, int kk) const { return lvl(sHS, hsM, hsP, ii, jj, kk); }
-  __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return sHC[(kk % HR) * (EW * (BY + 2)) + e(ii, jj)]; }
-  __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return sW[(kk % HR) * (EW * (BY + 2)) + e(ii, jj)]; }
-  __device__ __forceinline__ double maskW(int ii, int jj, int kk) const { return hFacW(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskS(int ii, int jj, int kk) const { return hFacS(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double maskC(int ii, int jj, int kk) const { return hFacC(ii, jj, kk) != 0.0 ? 1.0 : 0.0; }
-  __device__ __forceinline__ double recip_hFacW(int ii, int jj, int kk) const {
-    const double h = hFacW(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacS(int ii, int jj, int kk) const {
-    const double h = hFacS(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double recip_hFacC(int ii, int jj, int kk) const {
-    const double h = hFacC(ii, jj, kk); return h != 0.0 ? 1.0 / h : 0.0; }
-  __device__ __forceinline__ double h0FacW(int ii, int jj, int kk) const { return AR3(h0FacW, g(ii, jj, kk)); }
-  __device__ __forceinline__ double h0FacS(int ii, int jj, int kk) const { return AR3(h0FacS, g(ii, jj, kk)); }
+  __device__ __forceinline__ double hFacC(int ii, int jj, int kk) const { return sHC[(kk % 2) * (EW * (BY + 2)) + e(ii, jj)]; }
+  __device__ __forceinline__ double wVel(int ii, int jj, int kk) const { return sW[(kk % 2) * (EW * (BY + 2)) + e(ii, jj)]; }
   template <int F> __device__ __forceinline__ double g2(int ii, int jj) const {
-    constexpr int EN = EW * (BY + 2);
-    if constexpr (F == F2_dxC) return s2[0 * EN + e(ii, jj)];
-    else if constexpr (F == F2_dyC) return s2[1 * EN + e(ii, jj)];
-    else if constexpr (F == F2_recip_rAz) return s2[2 * EN + e(ii, jj)];
-    else if constexpr (F == F2_dxG) return s2[3 * EN + e(ii, jj)];
-    else if constexpr (F == F2_dyG) return s2[4 * EN + e(ii, jj)];
-    else if constexpr (F == F2_recip_rA) return s2[5 * EN + e(ii, jj)];
-    else {
-      if constexpr (OWN) {
-        const int di = ii - i, dj = jj - j;
-#define VM_R(name, DI, DJ, reg) if constexpr (F == F2_##name) { if (di == (DI) && dj == (DJ)) return c.reg; }
-        VM_R(recip_dxC, 0, 0, recip_dxC) VM_R(recip_dyC, 0, 0, recip_dyC) VM_R(recip_dxG, 0, 0, recip_dxG)
-        VM_R(recip_dyG, 0, 0, recip_dyG) VM_R(rAw, 0, 0, rAw) VM_R(rAs, 0, 0, rAs) VM_R(recip_rAw, 0, 0, recip_rAw)
-        VM_R(recip_rAs, 0, 0, recip_rAs) VM_R(dxV, 0, 0, dxV) VM_R(dxV, 0, 1, dxVn) VM_R(recip_dyU, 0, 0, recip_dyU)
-        VM_R(recip_dyU, 0, 1, recip_dyUn) VM_R(dyU, 0, 0, dyU) VM_R(dyU, 1, 0, dyUe) VM_R(recip_dxV, 0, 0, recip_dxV)
-        VM_R(recip_dxV, 1, 0, recip_dxVe) VM_R(fCoriG, 0, 0, fCoriG) VM_R(fCoriG, 0, 1, fCoriGn)
-        VM_R(fCoriG, 1, 0, fCoriGe) VM_R(rA, 0, 0, rA) VM_R(rA, -1, 0, rAw_w) VM_R(rA, 0, -1, rA_s)
-#undef VM_R
-      }
-      return f.a2[(long)F * d.N2all + MG_I2(d, ii, jj, t)];   // anything else: where it lies
-    }
+    return this->template g2_march<F, OWN>(EW * (BY + 2), ii, jj);
   }
-  __device__ __forceinline__ int iv(int ii, int jj) const { return (jj - j0) * IW + (ii - i0); }
-  __device__ __forceinline__ int id(int ii, int jj) const { return (jj - j0 + 1) * IW + (ii - i0 + 1); }
-  __device__ __forceinline__ double hfz(int ii, int jj) const { return sHfz[iv(ii, jj)]; }
-  __device__ __forceinline__ double h0fz(int ii, int jj) const { return sH0fz[iv(ii, jj)]; }
-  __device__ __forceinline__ double vort(int ii, int jj) const { return sVort[iv(ii, jj)]; }
-  __device__ __forceinline__ double KE(int ii, int jj) const { return sKE[id(ii, jj)]; }
-  __device__ __forceinline__ double hDiv(int ii, int jj) const { return sHDiv[id(ii, jj)]; }
 };
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ int vi_tile_face(const VIM2<BX, BY, P, OWN, HR> &a, const Fields &, int) { return a.face; }
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ int vi_tile_edge(const VIM2<BX, BY, P, OWN, HR> &a, const Fields &, int) { return a.edge; }
-template <int BX, int BY, class P, bool OWN, int HR>   // (called at kk = k and k + 1 only)
-__device__ __forceinline__ double vi_rdrC(const VIM2<BX, BY, P, OWN, HR> &a, const Fields &, int kk) {
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ int vi_tile_face(const VIM2<BX, BY, P, OWN> &a, const Fields &, int) { return a.face; }
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ int vi_tile_edge(const VIM2<BX, BY, P, OWN> &a, const Fields &, int) { return a.edge; }
+template <int BX, int BY, class P, bool OWN>   // (called at kk = k and k + 1 only)
+__device__ __forceinline__ double vi_rdrC(const VIM2<BX, BY, P, OWN> &a, const Fields &, int kk) {
   return kk == a.k ? a.rdrCk : a.rdrCk1;
 }
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ double vi_rdrF(const VIM2<BX, BY, P, OWN, HR> &a, const Fields &, int) { return a.rdrFk; }
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ double vi_drF(const VIM2<BX, BY, P, OWN, HR> &a, const Fields &, int) { return a.drFk; }
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ double vi_h0W_own(const VIM2<BX, BY, P, OWN, HR> &a, int, int, int) { return a.h0W; }
-template <int BX, int BY, class P, bool OWN, int HR>
-__device__ __forceinline__ double vi_h0S_own(const VIM2<BX, BY, P, OWN, HR> &a, int, int, int) { return a.h0S; }
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ double vi_rdrF(const VIM2<BX, BY, P, OWN> &a, const Fields &, int) { return a.rdrFk; }
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ double vi_drF(const VIM2<BX, BY, P, OWN> &a, const Fields &, int) { return a.drFk; }
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ double vi_h0W_own(const VIM2<BX, BY, P, OWN> &a, int, int, int) { return a.h0W; }
+template <int BX, int BY, class P, bool OWN>
+__device__ __forceinline__ double vi_h0S_own(const VIM2<BX, BY, P, OWN> &a, int, int, int) { return a.h0S; }
 
-// The k-march of k_mom_vi_march<PF, CREG> (same phases, same staging), on VIM2 / VIP<C>.
-// EARLY: the output point's own HBM reads of level k (phi_hyd at the three points of the
-// pressure gradient, guNm1, gvNm1) issued at the start of the level, in flight during the
-// ring-point intermediates, instead of after their barrier.  LBW: minimum waves per SIMD
-// the register allocation must allow (__launch_bounds__).
+// The k-march of k_mom_vi_march (same phases, same staging), on VIM2 / VIP<C>, in the form
+// that won (vi_m2_launch): the output point's metrics held in registers across the march;
+// its own HBM reads of level k (phi_hyd at the three points of the pressure gradient, guNm1,
+// gvNm1) issued at the start of the level, in flight during the ring-point intermediates,
+// instead of after their barrier; registers capped for 2 waves per SIMD.
 #ifdef MGCM_VI_STAMPS   // diagnostic build only: per-phase shader-cycle totals of sampled workgroups
 #define VI_STAMP(n)                                                          \
   do {                                                                       \
@@ -2033,8 +1776,8 @@ __device__ __forceinline__ double vi_h0S_own(const VIM2<BX, BY, P, OWN, HR> &a, 
   do {              \
   } while (0)
 #endif
-template <int BX, int BY, unsigned C, bool PF, bool CREG, bool EARLY, int LBW>
-__global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fields f, const int *iterPtr, int nbx, int nby,
+template <int BX, int BY, unsigned C>
+__global__ void __launch_bounds__(VT_NT, 2) k_mom_vi_m2(Dims d, VIP<C> p, Fields f, const int *iterPtr, int nbx, int nby,
                                                       int KC, int nkc) {
   using P = VIP<C>;
   constexpr int EW = BX + 2, EN = (BX + 2) * (BY + 2), IW = BX + 1, IN = (BX + 1) * (BY + 1);
@@ -2072,18 +1815,8 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
 #pragma unroll
       for (int r = 0; r < NR; r++) v2[n][r] = f.a2[(long)ids[n] * d.N2all + eq[r]];
   }
-  auto load_c = [&](VIMarchRegs &c, const long q2) {
-    const long qn = q2 + d.nx, qe = q2 + 1, qw = q2 - 1, qs = q2 - d.nx;
-    c.recip_dxC = AR2(recip_dxC, q2); c.recip_dyC = AR2(recip_dyC, q2);
-    c.recip_dxG = AR2(recip_dxG, q2); c.recip_dyG = AR2(recip_dyG, q2);
-    c.rAw = AR2(rAw, q2); c.rAs = AR2(rAs, q2); c.recip_rAw = AR2(recip_rAw, q2); c.recip_rAs = AR2(recip_rAs, q2);
-    c.dxV = AR2(dxV, q2); c.dxVn = AR2(dxV, qn); c.recip_dyU = AR2(recip_dyU, q2); c.recip_dyUn = AR2(recip_dyU, qn);
-    c.dyU = AR2(dyU, q2); c.dyUe = AR2(dyU, qe); c.recip_dxV = AR2(recip_dxV, q2); c.recip_dxVe = AR2(recip_dxV, qe);
-    c.fCoriG = AR2(fCoriG, q2); c.fCoriGn = AR2(fCoriG, qn); c.fCoriGe = AR2(fCoriG, qe);
-    c.rA = AR2(rA, q2); c.rAw_w = AR2(rA, qw); c.rA_s = AR2(rA, qs);
-  };
-  VIMarchRegs c0;
-  if constexpr (CREG) load_c(c0, q2);
+  VIMarchRegs c;   // loaded once, live in registers across the march
+  c.load(d, f, q2);
   const int tFace = P::cubeCorners ? f.tileFace[t] : 0, tEdge = P::cubeCorners ? f.tileEdge[t] : 0;
   const long t3 = (long)t * (d.n3 - d.n2);
   const unsigned lvB = (unsigned)(d.n2 * 8);
@@ -2166,7 +1899,6 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
   const int myIter = *iterPtr;
   const double abFac = (myIter == p.nIter0 && p.nIter0 == 0) ? 0.0 : 0.5 + p.abEps;   // adams_bashforth2.F:61-65
   const double mass2rUnit = 1.0 / p.rhoConst;
-  constexpr bool rstar = P::nonlinFreeSurf > 0 && P::select_rStar > 0;
   __syncthreads();
 #ifdef MGCM_VI_STAMPS
   unsigned long long viAcc[6] = {0, 0, 0, 0, 0, 0}, viPrev = 0;
@@ -2186,29 +1918,20 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
     asm volatile("" : "+s"(fl.a2), "+s"(fl.a3), "+s"(dl.N2all), "+s"(dl.N3all));
     const Fields &f = fl;
     const Dims &d = dl;
-    VIMarchRegs c1;
-    if constexpr (!CREG) load_c(c1, q2);
-    const VIMarchRegs &c = CREG ? c0 : c1;
-    const int kn = k + 1 <= Nr ? k + 1 : Nr, kw = k + 2 <= Nr ? k + 2 : Nr;
-    if constexpr (PF) {
-      fetch(kn);
-      fetchW(kw);
-    } else {
-      const unsigned o = ob + (unsigned)(kn - 1) * lvB;
+    {   // own column at k+1; the level itself is fetched after the output
+      const unsigned o = ob + (unsigned)((k + 1 <= Nr ? k + 1 : Nr) - 1) * lvB;
       oU = ld(bU, o); oV = ld(bV, o); oHW = ld(bHW, o); oHS = ld(bHS, o);
     }
-    // EARLY: the level's own-point HBM reads, before the intermediates' barrier (the
+    // the level's own-point HBM reads, before the intermediates' barrier (the
     // pressure-gradient phi_hyd values of the linear free surface / non-rsc r* case only)
-    constexpr bool rscE = rstar && P::select_rStar >= 2 && P::nonlinFreeSurf >= 4;
-    double ePhi0 = 0.0, ePhiX = 0.0, ePhiY = 0.0, eGuo = 0.0, eGvo = 0.0;
-    if constexpr (EARLY) {
-      const long q3e = q2 + (long)(k - 1) * d.n2 + t3;
-      eGuo = AR3(guNm1, q3e); eGvo = AR3(gvNm1, q3e);
-      if constexpr (!rscE) { ePhi0 = AR3(phiHydC, q3e); ePhiX = AR3(phiHydC, q3e - 1); ePhiY = AR3(phiHydC, q3e - d.nx); }
-    }
-    VIM2<BX, BY, P, true> a{d, p, f, k, t, i0, j0, i, j, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
+    constexpr bool rscE = P::nonlinFreeSurf >= 4 && P::select_rStar >= 2;
+    const long q3 = q2 + (long)(k - 1) * d.n2 + t3;
+    const double eGuo = AR3(guNm1, q3), eGvo = AR3(gvNm1, q3);
+    double ePhi0 = 0.0, ePhiX = 0.0, ePhiY = 0.0;
+    if constexpr (!rscE) { ePhi0 = AR3(phiHydC, q3); ePhiX = AR3(phiHydC, q3 - 1); ePhiY = AR3(phiHydC, q3 - d.nx); }
+    VIM2<BX, BY, P, true> a{{}, d, p, f, k, t, i0, j0, i, j, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
                             uM, k < Nr ? oU : 0.0, vM, k < Nr ? oV : 0.0, hwM, k < Nr ? oHW : 0.0, hsM, k < Nr ? oHS : 0.0};
-    VIM2<BX, BY, P, false> ai{d, p, f, k, t, i0, j0, 0, 0, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
+    VIM2<BX, BY, P, false> ai{{}, d, p, f, k, t, i0, j0, 0, 0, sU, sV, sHW, sHS, sHC, sW, s2, sKE, sVort, sHfz, sH0fz, sHDiv, c,
                               0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // the level's 1-D factors and the own point's rest-state thicknesses, fetched here with
     // the level's other reads (vi_rdrC ... overloads)
@@ -2219,49 +1942,37 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
     a.rdrFk = f.recip_drF[k - 1];
     a.drFk = f.drF[k - 1];
     if constexpr (P::momViscosity && P::no_slip_sides) {
-      const long q3h = q2 + (long)(k - 1) * d.n2 + t3;
-      a.h0W = AR3(h0FacW, q3h);
-      a.h0S = AR3(h0FacS, q3h);
+      a.h0W = AR3(h0FacW, q3);
+      a.h0S = AR3(h0FacS, q3);
     }
-    for (int q = tid; q < IN; q += VT_NT) {
-      const int ii = i0 + q % IW, jj = j0 + q / IW;          // vort / hFacZ grid: i0..i0+BX
-      const bool ok = ii <= d.sNx + d.OLx && jj <= d.sNy + d.OLy;
-      sHfz[q] = ok ? vi_hfacz(ai, d, ii, jj, k) : 0.0;
-      sH0fz[q] = ok ? vi_h0facz(ai, d, p, ii, jj, k) : 0.0;
-      sVort[q] = ok ? vi_vort(ai, d, p, f, ii, jj, k, t) : 0.0;
-      sKE[q] = vi_KE(ai, d, p, f, ii - 1, jj - 1, k, t);     // KE / hDiv grid: i0-1..i0+BX-1
-      sHDiv[q] = vi_hdiv(ai, d, p, f, ii - 1, jj - 1, k, t);
-    }
+    vi_intermediates(ai, d, p, f, tid, IN);
     VI_STAMP(1);
     __syncthreads();
     VI_STAMP(2);
     if (act) {
-      auto q3of = [&](long qq2, int kk) { return qq2 + (long)(kk - 1) * d.n2 + t3; };
-      const long q3 = q3of(q2, k);
+      // one component at a time: tendency, AB2, store, each from its own vecinv_tend call whose
+      // other outputs are dead (the compiler drops their arithmetic; the common reads are
+      // shared), a scheduling barrier between the two so the halves' live values do not
+      // overlap: 215 against 247 VGPRs at 2 waves per SIMD, LLC-90's VI 319-320 against
+      // 323.7-323.8 us with both chains interleaved (round 6, profiles/r06/ab_hr_vi/); capped
+      // for 3 waves per SIMD the split form still spills 43 VGPRs (605 us).  The arithmetic is
+      // vi_point_tail's, one component of it: calling that here with a component selector
+      // measured 318.1-319.2 against the parent's 316.2-317.2 us (profiles/r15/vi_family/)
+      constexpr bool rstar = P::nonlinFreeSurf > 0 && P::select_rStar > 0;
       const double recip_drF = a.rdrFk;
-      // one component at a time (CC 1: U, 2: V): tendency, AB2, store, each from its own
-      // vecinv_tend call whose other outputs are dead (the compiler drops their arithmetic;
-      // the common reads are shared), a scheduling barrier between the two so the halves' live
-      // values do not overlap: 215 against 247 VGPRs at 2 waves per SIMD, LLC-90's VI 319-320
-      // against 323.7-323.8 us with both chains interleaved (round 6, profiles/r06/ab_hr_vi/);
-      // capped for 3 waves per SIMD the split form still spills 43 VGPRs (605 us)
       auto comp = [&](auto tagC) {
         constexpr int CC = decltype(tagC)::value;   // 1: U, 2: V
         double gU = 0.0, gV = 0.0, guDiss = 0.0, gvDiss = 0.0, dPhiHydX = 0.0, dPhiHydY = 0.0;
         {  // CALC_GRAD_PHI_HYD (calc_grad_phi_hyd.F:152-214), as k_mom_step
-          constexpr bool rsc = rstar && P::select_rStar >= 2 && P::nonlinFreeSurf >= 4;
-          auto varLoc = [&](long qq2) {
-            if constexpr (rsc) return AR3(phiHydC, q3of(qq2, k)) * AR2(rStarFacC, qq2) + 0.0;
-            else return AR3(phiHydC, q3of(qq2, k)) + 0.0;
-          };
-          if constexpr (EARLY && !rsc) {
+          auto varLoc = [&](long o) { return AR3(phiHydC, q3 - o) * AR2(rStarFacC, q2 - o) + 0.0; };   // rscE only
+          if constexpr (!rscE) {
             const double vl = ePhi0 + 0.0;
             if (CC == 1 && i >= 1) dPhiHydX = c.recip_dxC * (vl - (ePhiX + 0.0));
             if (CC == 2 && j >= 1) dPhiHydY = c.recip_dyC * (vl - (ePhiY + 0.0));
           } else {
-            const double vl = varLoc(q2);
-            if (CC == 1 && i >= 1) dPhiHydX = c.recip_dxC * (vl - varLoc(q2 - 1));
-            if (CC == 2 && j >= 1) dPhiHydY = c.recip_dyC * (vl - varLoc(q2 - d.nx));
+            const double vl = varLoc(0);
+            if (CC == 1 && i >= 1) dPhiHydX = c.recip_dxC * (vl - varLoc(1));
+            if (CC == 2 && j >= 1) dPhiHydY = c.recip_dyC * (vl - varLoc(d.nx));
           }
           if constexpr (rstar && P::select_rStar >= 2) {
             const double factorP = p.gravity * (1.0 / p.rhoConst) * 0.5, rCk = f.rC[k - 1];
@@ -2284,8 +1995,7 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
         if (P::momViscosity && P::momDissip_In_AB) g = g + gDiss;
         if (P::momForcing && P::momForcingOutAB != 1) g = g + gExt;
         {  // ADAMS_BASHFORTH2 (adams_bashforth2.F:81-88)
-          const double go = CC == 1 ? (EARLY ? eGuo : AR3(guNm1, q3)) : (EARLY ? eGvo : AR3(gvNm1, q3));
-          const double ab = abFac * (g - go);
+          const double ab = abFac * (g - (CC == 1 ? eGuo : eGvo));
           if (CC == 1) AR3(guNm1, q3) = g; else AR3(gvNm1, q3) = g;
           g = g + ab;
         }
@@ -2304,10 +2014,8 @@ __global__ void __launch_bounds__(VT_NT, LBW) k_mom_vi_m2(Dims d, VIP<C> p, Fiel
     }(iL, jL, q2L);
     if (k == ke) break;
     if (act) { const int eo = (j - j0 + 1) * EW + (i - i0 + 1); uM = sU[eo]; vM = sV[eo]; hwM = sHW[eo]; hsM = sHS[eo]; }
-    if constexpr (!PF) {
-      fetch(k + 1 <= Nr ? k + 1 : Nr);
-      fetchW(k + 2 <= Nr ? k + 2 : Nr);
-    }
+    fetch(k + 1 <= Nr ? k + 1 : Nr);
+    fetchW(k + 2 <= Nr ? k + 2 : Nr);
     __syncthreads();
     VI_STAMP(4);
     stash(k + 1);
@@ -2400,11 +2108,11 @@ constexpr unsigned vi_code(int vs, int cs, int ks, int visc, int nss, int nsb, i
          (unsigned)nlfs << 17 | (unsigned)rstar << 20;
 }
 constexpr unsigned VI_CODE_LLC = vi_code(1, 0, 0, 1, 1, 1, 0, 1, 1, 0, 1, 1, 1, 0, 0, 0);
-template <int BX, int BY, unsigned C, int V>
+template <int BX, int BY, unsigned C>
 static void vi_m2_one(const Dims &d, const VIP<C> &vp, const Fields &f, const int *iterPtr, int nbx, int nby, int KC,
                       int nkc, hipStream_t s) {
-  hipLaunchKernelGGL((k_mom_vi_m2<BX, BY, C, (V & 1) != 0, (V & 2) != 0, (V & 4) != 0, (V & 8) ? 2 : 1>),
-                     dim3((unsigned)(nbx * nby * d.nT * nkc)), dim3(VT_NT), 0, s, d, vp, f, iterPtr, nbx, nby, KC, nkc);
+  hipLaunchKernelGGL((k_mom_vi_m2<BX, BY, C>), dim3((unsigned)(nbx * nby * d.nT * nkc)), dim3(VT_NT), 0, s, d, vp, f, iterPtr,
+                     nbx, nby, KC, nkc);
 }
 // k_mom_vi_m2 as launched: the output point's metrics held in registers across the march
 // (CREG), its own HBM reads of a level issued at the level's start (EARLY), registers capped
@@ -2419,17 +2127,17 @@ static bool vi_m2_launch(const Dims &d, const Params &p, const Fields &f, const 
                          int nby, int KC, int nkc, hipStream_t s) {
   const unsigned code = vi_opt_code(p);
   if (code == VI_CODE_LLC && BX == 31 && BY == 8) {
-    vi_m2_one<31, 8, VI_CODE_LLC, 14>(d, vi_params<VI_CODE_LLC>(p), f, iterPtr, nbx, nby, KC, nkc, s);
+    vi_m2_one<31, 8, VI_CODE_LLC>(d, vi_params<VI_CODE_LLC>(p), f, iterPtr, nbx, nby, KC, nkc, s);
     return true;
   }
   if (code == VI_CODE_LLC && BX == 32 && BY == 8) {
-    vi_m2_one<32, 8, VI_CODE_LLC, 14>(d, vi_params<VI_CODE_LLC>(p), f, iterPtr, nbx, nby, KC, nkc, s);
+    vi_m2_one<32, 8, VI_CODE_LLC>(d, vi_params<VI_CODE_LLC>(p), f, iterPtr, nbx, nby, KC, nkc, s);
     return true;
   }
   return false;
 }
 
-// block shape of k_mom_vi_tiled: BX along i (a whole output row when it is short), BY rows
+// block shape of the staged VI kernels: BX along i (a whole output row when it is short), BY rows
 static void vi_tile_shape(const Dims &d, int &BX, int &BY) {
   const int W = d.sNx + 2, H = d.sNy + 2;
   const int nbx = (W + 31) / 32;
@@ -2619,10 +2327,10 @@ static bool vi_march_path(const Dims &d, const Params &p) {
   return p.vectorInvariantMomentum && d.OLx >= 2 && d.OLy >= 2 && p.selectVortScheme <= 2;
 }
 bool mom_ring_separable(const Dims &d, const Params &p) {
-  return vi_march_path(d, p) && !p.useCDscheme && 2 * (d.OLy - 1) * d.nx + (d.sNy + 2) * 2 * (d.OLx - 1) > 0;
+  return vi_march_path(d, p) && !p.useCDscheme && mom_halo_ring_count_host(d) > 0;
 }
 hipError_t launch_mom_ring(const Dims &d, const Params &p, const Fields &f, const int *iterPtr, hipStream_t s) {
-  const int ring = 2 * (d.OLy - 1) * d.nx + (d.sNy + 2) * 2 * (d.OLx - 1);
+  const int ring = mom_halo_ring_count_host(d);
   if (ring > 0)
     hipLaunchKernelGGL(k_mom_halo_ab, dim3((unsigned)((ring + 255) / 256), d.Nr, d.nT), dim3(256), 0, s, d, p, f, iterPtr);
   return hipGetLastError();
@@ -2640,9 +2348,9 @@ hipError_t launch_mom_step(const Dims &d, const Params &p, const Fields &f, cons
     // with >= 256 workgroups per level chunk), in two chunks of levels (round 4, k_mom_vi_m2:
     // LLC-90 448-456 us against 460 at five and 453-460 at three, step 1.531-1.545 against
     // 1.550-1.552 ms, profiles/r04/vikc/) or one (below); otherwise one level per
-    // workgroup.  MGCM_VI_KERNEL = march | march_generic | level | tiled forces a form (the
-    // tests run each: march_generic is the generic k-march that serves option sets without
-    // a k_mom_vi_m2 instantiation; read per launch)
+    // workgroup.  MGCM_VI_KERNEL = march | march_generic | level forces a form (the tests run
+    // each: march_generic is the generic k-march that serves option sets without a
+    // k_mom_vi_m2 instantiation; any other value: level; read per launch)
     const char *viEnv = getenv("MGCM_VI_KERNEL");
     const int nbt = nbx * nby * d.nT;
     // Round 6: the whole column per workgroup where the blocks then fit one resident round (2
@@ -2656,15 +2364,11 @@ hipError_t launch_mom_step(const Dims &d, const Params &p, const Fields &f, cons
     if (march) {
       const int nkc = (d.Nr + KCm - 1) / KCm;
       if (generic || !vi_m2_launch(d, p, f, iterPtr, BX, BY, nbx, nby, KCm, nkc, s))
-        hipLaunchKernelGGL((k_mom_vi_march<false, false>), dim3((unsigned)(nbt * nkc)), dim3(VT_NT), 0, s, d, p, f, iterPtr,
-                           BX, BY, nbx, nby, KCm, nkc);
-    } else if (!(viEnv && !strcmp(viEnv, "tiled"))) {   // one level per workgroup
+        hipLaunchKernelGGL(k_mom_vi_march, dim3((unsigned)(nbt * nkc)), dim3(VT_NT), 0, s, d, p, f, iterPtr, BX, BY, nbx,
+                           nby, KCm, nkc);
+    } else {   // one level per workgroup
       hipLaunchKernelGGL(k_mom_vi_level, dim3((unsigned)(nbx * nby * d.nT * d.Nr)), dim3(VT_NT), 0, s, d, p, f, iterPtr, BX,
                          BY, nbx, nby);
-    } else {            // KCm levels marched per workgroup, the tiled form
-      const int nkc = (d.Nr + KCm - 1) / KCm;
-      hipLaunchKernelGGL(k_mom_vi_tiled, dim3((unsigned)(nbt * nkc)), dim3(VT_NT), 0, s, d, p, f, iterPtr, BX, BY, nbx,
-                         nby, KCm, nkc);
     }
     if (ring || p.useCDscheme) launch_mom_ring(d, p, f, iterPtr, s);
   } else if (p.vectorInvariantMomentum)
