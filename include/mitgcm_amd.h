@@ -126,6 +126,14 @@ double *mgcm_device_ptr(mgcm_model *m, const char *name);
  * offset (tile,j,i) it copies from, or -1 to leave it untouched. */
 int mgcm_set_halo_map(mgcm_model *m, const long *src_of_point, long count);
 
+/* The halo map as the table of records the end-of-step kernels read (host only, no model, no
+ * device; csrc/common.h HaloRec): for each of the nTiles*(sNx+2OLx)*(sNy+2OLy) points q, four
+ * ints -- at = src_of_point[q] if >= 0 else q; (at / n2) * n3 + at % n2, the base of at's 3-D
+ * column (n2 points per tile and level, n3 = n2 * Nr); (i & 0xffff) | (j << 16), at's (i, j) in
+ * its tile; flags, 1: q is interior, 2: q has a source.  Returns -1, out untouched, where an
+ * offset does not fit 32 bits. */
+int mgcm_halo_table(int sNx, int sNy, int OLx, int OLy, int Nr, int nTiles, const long *src_of_point, int *out);
+
 /* EXCH2 C-grid vector maps (pkg/exch2/exch2_uv_3d_rx.template), for EXCH_UV_XY(Z)_RL with
  * withSigns = .TRUE. (u1, v1) and .FALSE. (u0, v0): per point of u and of v, 0 = untouched,
  * +(src+1) / -(src+1) = copy (minus) the value at src, which indexes [u | v] (2*count);

@@ -264,7 +264,7 @@ inline size_t mg_colf_lds(int Nr, int nc, int nArr) { return (size_t)nArr * Nr *
   } while (0)
 inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + nc - 1) / nc); }
 // Launch fusions of FORWARD_STEP, each switchable for A/B runs: MGCM_STEP_FUSE = bit mask of
-// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP | SPEC): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
+// the enabled ones (default SFP | PHI | END | DT | ETAX | OPE | RING | RINGP | ENDS | PIPE | PHIP | SPEC | SPEC2): MG_FUSE_SFP CALC_DIV_GHAT in the r* column pass,
 // MG_FUSE_PHI CALC_PHI_HYD + del2uv in one grid, MG_FUSE_END CALC_R_STAR + the blocking
 // exchanges in one grid, MG_FUSE_TREX the
 // tracers' halo exchange on their own stream beside the pressure solve (late join only;
@@ -285,6 +285,9 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 // MG_FUSE_SPEC no launch fusion but a choice of instantiation: the fold's second and third grid
 // (k_dt_l2, k_dt_l3) compiled for global_ocean.90x40x15's option set (OptsGO90 below) where the
 // model's options are that set; bit-identical, every other configuration runs the generic ones.
+// MG_FUSE_SPEC2 (with MG_FUSE_SPEC, in the pipelined step) the same choice for the grids on either
+// side of the pressure solve: UPDATE_R_STAR's column pass with its riders and the correction step
+// with the next step's tensor (k_update_r_star_cg2d_a<true, 2, OptsGO90>, k_corr_cont<true, OptsGO90>).
 // The step's fusions are decided in one place, model.hip's plan_step; the kernel files' own
 // *_fusable / *_ok predicates, which it calls, read their bits here too.
 // Four bits are retired (round 10): each was off by default, bit-identical and measured slower
@@ -303,15 +306,16 @@ inline unsigned mg_colf_blocks(long ncols, int nc) { return (unsigned)((ncols + 
 //       UPDATE_R_STAR rewrites it: on config 2 the fold into DYNAMICS' launches stays faster,
 //       0.2885 against 0.307 ms/step (profiles/r04/tcg/) -- the tracers' launches beside
 //       DYNAMICS cost more than the 190 us single-CU solve they could hide behind.
-// The thirteen others keep their values (tests and tools pass numeric masks).
+// The fourteen others keep their values (tests and tools pass numeric masks).
 enum { MG_FUSE_SFP = 1, MG_FUSE_PHI = 4, MG_FUSE_END = 8, MG_FUSE_TREX = 64, MG_FUSE_DT = 128, MG_FUSE_ETAX = 256,
        MG_FUSE_OPE = 1024, MG_FUSE_RING = 2048, MG_FUSE_RINGP = 4096, MG_FUSE_ENDS = 8192, MG_FUSE_PIPE = 16384,
-       MG_FUSE_PHIP = 32768, MG_FUSE_SPEC = 65536 };
+       MG_FUSE_PHIP = 32768, MG_FUSE_SPEC = 65536, MG_FUSE_SPEC2 = 131072 };
 inline int mg_fuse_mask() {
   // read per call (tests switch it per model)
   return getenv("MGCM_STEP_FUSE") ? atoi(getenv("MGCM_STEP_FUSE"))
                                   : MG_FUSE_SFP | MG_FUSE_PHI | MG_FUSE_END | MG_FUSE_DT | MG_FUSE_ETAX | MG_FUSE_OPE |
-                                        MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE | MG_FUSE_PHIP | MG_FUSE_SPEC;
+                                        MG_FUSE_RING | MG_FUSE_RINGP | MG_FUSE_ENDS | MG_FUSE_PIPE | MG_FUSE_PHIP | MG_FUSE_SPEC |
+                                        MG_FUSE_SPEC2;
 }
 inline bool mg_fuse_on(int bit) { return (mg_fuse_mask() & bit) != 0; }
 // the lowest retired bit the mask sets (0: none), and what it selected
@@ -374,7 +378,23 @@ inline unsigned mg_plane_blocks(int ni, int nj, int nz) {
   X(gmAdvForm, p.GM_AdvForm != 0, false)                                                            \
   X(gmExtraDiag, p.GM_ExtraDiag != 0, false)                                                        \
   X(implicitDiffusion, p.implicitDiffusion != 0, true)                                              \
-  X(tracForcingOutAB, p.tracForcingOutAB != 0, false)
+  X(tracForcingOutAB, p.tracForcingOutAB != 0, false)                                               \
+  /* the solve-side grids' questions (MG_FUSE_SPEC2).  quasiHydrostatic, storePhiHyd4Phys and      \
+     cubeCorners are asked by no compiled body (a pinned k_rstar_exch_phi was not kept) and       \
+     opEveryStep only by the generic r* pass: they are listed to narrow opts_match to             \
+     global_ocean.90x40x15 itself, so a model off any of them runs every generic kernel */        \
+  X(exactConserv, p.exactConserv != 0, true)                                                        \
+  X(realFreshWaterFlux, p.useRealFreshWaterFlux != 0, true)                                         \
+  X(quasiHydrostatic, p.quasiHydrostatic != 0, true)                                                \
+  X(storePhiHyd4Phys, p.storePhiHyd4Phys != 0, true)                                                \
+  X(eosPresFromPhi, p.selectP_inEOS_Zc == 2, true)   /* JMD95P */                                   \
+  X(eosJmd95, p.eosType == 1, true)                                                                 \
+  X(allowFreezing, p.allowFreezing != 0, true)                                                      \
+  X(periodicForcing, p.periodicExternalForcing != 0, true)                                          \
+  X(gmRedi, p.useGMRedi != 0, true)                                                                 \
+  X(ivdc, p.ivdc_kappa != 0.0, true)                                                                \
+  X(opEveryStep, p.nonlinFreeSurf > 2, true)   /* UPDATE_CG2D every step */                        \
+  X(cubeCorners, p.cubeCorners != 0, false)
 struct OptsRun {
   static constexpr bool pinned = false;
 #define MG_OPT_RUN(name, expr, pin) \
@@ -401,14 +421,15 @@ inline bool opts_match(const Params &p) {
 // The serial end of SOLVE_FOR_PRESSURE's right-hand side for one column (k_sfp_rhs and the
 // fused r* pass k_update_r_star_cg2d_a<SFP>): etaNm1 (CD scheme), cg2d_x = Bo_surf*etaN and
 // cg2d_b = CALC_DIV_GHAT's k = Nr..1 sum of the staged flux terms + the free-surface term.
+template <class O = OptsRun>
 __device__ __forceinline__ void sfp_rhs_column(const Dims &d, const Params &p, const Fields &f, long q, bool inner,
                                                const double *sE, const double *sW, const double *sN, const double *sS,
                                                int NC_, int cc) {
-  if (p.useCDscheme) f.etaNm1[q] = f.etaN[q];
+  if (O::cdScheme(p)) f.etaNm1[q] = f.etaN[q];
   f.cg2d_x[q] = f.Bo_surf[q] * f.etaN[q];
   double b = 0.0;
   if (inner) {
-    if (p.useRealFreshWaterFlux) {
+    if (O::realFreshWaterFlux(p)) {
       const double tmpFac = p.freeSurfFac * (1.0 / p.rhoConst) * p.implicDiv2DFlow;
       b = tmpFac * f.rA[q] * f.EmPmR[q] / p.deltaTMom * f.maskInC[q];
     }
@@ -418,7 +439,7 @@ __device__ __forceinline__ void sfp_rhs_column(const Dims &d, const Params &p, c
       b = b + sN[s2] - sS[s2];
     }
     // solve_for_pressure.F:214-236 (linear free surface): etaH with exactConserv, else etaN
-    b = b - p.freeSurfFac * f.rA[q] / p.deltaTMom / p.deltaTFreeSurf * (p.exactConserv ? f.etaH[q] : f.etaN[q]);
+    b = b - p.freeSurfFac * f.rA[q] / p.deltaTMom / p.deltaTFreeSurf * (O::exactConserv(p) ? f.etaH[q] : f.etaN[q]);
   }
   f.cg2d_b[q] = b;
 }
@@ -458,6 +479,26 @@ struct TracerArgs {
 __device__ __forceinline__ double ptr_surf_relax(const TracerArgs &a, double trSurf, double drF1, double hFacC1) {
   return (((a.relaxRate * (a.relaxVal - trSurf)) * drF1) * hFacC1);
 }
+
+// (i, j) of the 2-D offset q
+__host__ __device__ __forceinline__ void mg_ij_of(const Dims &d, long q, int &i, int &j) {
+  const long l = q % d.n2;
+  i = (int)(l % d.nx) - d.OLx + 1;
+  j = (int)(l / d.nx) - d.OLy + 1;
+}
+
+// The halo topology of one 2-D point as a record, for the bodies that read a field the exchange
+// is still filling (rstar.h, kernels_dyn.hip; the riders of k_rstar_exch_phi): what they would
+// otherwise derive from srcOf[q] with 64-bit division, per thread and per step, though it is fixed
+// when the exchange map is.  Built on the host beside srcOf (model.hip mg_build_halo_table), 32-bit
+// (grids of fewer than 2^31 3-D points per field), 16 bytes: one load.
+enum { MG_HR_INTERIOR = 1, MG_HR_MAPPED = 2 };
+struct __attribute__((aligned(16))) HaloRec {
+  int at2;      // the 2-D offset at which the point's value lives: its exchange source, else itself
+  int base3;    // that offset as the base of a 3-D column: (at2 / n2) * n3 + at2 % n2
+  short i, j;   // (i, j) of at2 within its tile
+  int flags;    // MG_HR_INTERIOR: the point is interior; MG_HR_MAPPED: it has an exchange source
+};
 
 // Fields exchanged together by k_exchange_multi.
 #define MG_XMAX 8

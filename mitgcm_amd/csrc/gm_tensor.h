@@ -29,6 +29,8 @@ __device__ __forceinline__ void gm_slope_gkw91(const Params &p, double dSx, doub
   else if (SlopeSqr > maxSlopeSqr && SlopeSqr < p.GM_slopeSqCutoff) taper = maxSlopeSqr / SlopeSqr;
 }
 
+// O: the option set the body is compiled for (common.h)
+template <class O = OptsRun>
 __device__ __forceinline__ void gm_tensor_body(const Dims &d, const Params &p, const Fields &f, int lb) {
   MG_PLANE_LB(2 - d.OLx, d.nx - 2, 2 - d.OLy, d.ny - 2, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
@@ -69,7 +71,7 @@ __device__ __forceinline__ void gm_tensor_body(const Dims &d, const Params &p, c
     const double dSr = op25 * (sR(i - 1, j, k) + sR(i, j, k) + (sR(i - 1, j, kp1) + sR(i, j, kp1)) * maskp1) * mW * gs;
     gm_slope_gkw91(p, dSx, dSy, dSr, SlopeX, SlopeY, SlopeSqr, taper);
     f.Kux[q3] = fmax((p.GM_isopycK * 1.0 * op5 * (1.0 + 1.0)) * taper, p.GM_Kmin_horiz);
-    if (p.GM_ExtraDiag)   // GM_EXTRA_DIAGONAL Kuz (gmredi_calc_tensor.F:808-850)
+    if (O::gmExtraDiag(p))   // GM_EXTRA_DIAGONAL Kuz (gmredi_calc_tensor.F:808-850)
       f.Kuz[q3] = -gs * (p.GM_isopycK * 1.0 * op5 * (1.0 + 1.0) - p.GM_skewflx * p.GM_background_K * 1.0 * op5 * (1.0 + 1.0)) *
                   SlopeX * taper;
   }
@@ -80,11 +82,11 @@ __device__ __forceinline__ void gm_tensor_body(const Dims &d, const Params &p, c
     const double dSr = op25 * (sR(i, j - 1, k) + sR(i, j, k) + (sR(i, j - 1, kp1) + sR(i, j, kp1)) * maskp1) * mS * gs;
     gm_slope_gkw91(p, dSx, dSy, dSr, SlopeX, SlopeY, SlopeSqr, taper);
     f.Kvy[q3] = fmax((p.GM_isopycK * 1.0 * op5 * (1.0 + 1.0)) * taper, p.GM_Kmin_horiz);
-    if (p.GM_ExtraDiag)   // Kvz (gmredi_calc_tensor.F:1053-1090)
+    if (O::gmExtraDiag(p))   // Kvz (gmredi_calc_tensor.F:1053-1090)
       f.Kvz[q3] = -gs * (p.GM_isopycK * 1.0 * op5 * (1.0 + 1.0) - p.GM_skewflx * p.GM_background_K * 1.0 * op5 * (1.0 + 1.0)) *
                   SlopeY * taper;
   }
-  if (p.GM_AdvForm) {
+  if (O::gmAdvForm(p)) {
     // GMREDI_CALC_PSI_B (gmredi_calc_psi_b.F:86-212) + GMREDI_SLOPE_PSI gkw91
     // (gmredi_slope_psi.F:196-290): bolus stream-function at the top face of level k >= 2
     double psx = 0.0, psy = 0.0;

@@ -48,10 +48,11 @@ __device__ __forceinline__ double h0facz(const Dims &d, const Params &p, const F
 // the Laplacians of u and v the biharmonic viscous fluxes difference, with the no-slip
 // side-wall term from the rest-state h0Fac (NONLIN_FRSURF).
 // HO (MG_FUSE_PHIP): the pass of the next step inside this step's end-of-step exchange grid, which
-// is filling the halos of u and v: every u, v is read at its exchange source (mg_at_source3).
+// is filling the halos of u and v: every u, v is read at its exchange source (mg_at_source3, from
+// the HaloRec table).
 template <bool HO = false>
 __device__ __forceinline__ void del2uv_body(const Dims &d, const Params &p, const Fields &f, int lb,
-                                            const long *__restrict__ srcOf = nullptr) {
+                                            const HaloRec *__restrict__ rec = nullptr) {
   MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   const long q3 = MG_I3(d, i, j, k, t);
@@ -62,7 +63,9 @@ __device__ __forceinline__ void del2uv_body(const Dims &d, const Params &p, cons
   }
   const double drF = f.drF[k - 1];
   // the five points u and v are read at: (i,j), (i-1,j), (i+1,j), (i,j-1), (i,j+1)
-  auto uv3 = [&](int ii, int jj) { return HO ? mg_at_source3(d, srcOf, ii, jj, k, t) : MG_I3(d, ii, jj, k, t); };
+  auto uv3 = [&](int ii, int jj) {
+    return HO ? mg_at_source3(d, rec, ii, jj, t) + (long)(k - 1) * d.n2 : MG_I3(d, ii, jj, k, t);
+  };
   const long qv[5] = {uv3(i, j), uv3(i - 1, j), uv3(i + 1, j), uv3(i, j - 1), uv3(i, j + 1)};
   auto qvAt = [&](int ii, int jj) { return qv[jj == j ? (ii == i ? 0 : ii < i ? 1 : 2) : (jj < j ? 3 : 4)]; };
 #define U(ii, jj) f.uVel[HO ? qvAt(ii, jj) : MG_I3(d, ii, jj, k, t)]
@@ -122,15 +125,18 @@ __global__ void __launch_bounds__(256) k_del2uv(Dims d, Params p, Fields f) { de
 // HO (MG_FUSE_PHIP, r* only): the pass of the NEXT step inside this step's last grid, beside
 // CALC_R_STAR + UPDATE_ETAH and the blocking exchanges (k_rstar_exch_phi, kernels_step.hip).  The
 // same expression trees on the values the next step's own pass would read:
-//   - uVel, vVel of the QH buoyancy terms at their exchange sources (mg_at_source3);
+//   - uVel, vVel of the QH buoyancy terms at their exchange sources (mg_at_source3: the three
+//     columns' level-1 offsets are taken from the HaloRec table once, ahead of the level loop);
 //   - rStarFacC and rStarDh{C,W,S}Dt, which CALC_R_STAR's blocks are storing, formed here by the
 //     same expressions from the factors kept in rStarFac*Prev (rstar.h r_star_next_point);
 //   - rhoInSitu, h0Fac and the geometry in place (nothing in the grid writes them);
 //   - totPhiHyd is stored on the ring 0 / sN+1 too, so a step that carries this pass leaves
 //     totPhiHyd out of its exchange (model.hip one_step).
+// It needs Nr >= 2 (phi_pipe_ok): the serial thread's d0 of the west and south neighbours are
+// always handed over by two other level slots, so the body holds one copy of that expression.
 template <bool HO = false>
 __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, const Fields &f, int nc, int lb,
-                                             const long *__restrict__ srcOf = nullptr, int fromX = 0) {
+                                             const HaloRec *__restrict__ rec = nullptr, int fromX = 0) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   MG_COLF_LB(-1, d.sNx + 3, -1, d.sNy + 3, nc, lb)
   const int Nr = d.Nr, NS = Nr * NC_;
@@ -143,13 +149,21 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
   double hoFacC = 0.0, hoDhC = 0.0, hoDhW = 0.0, hoDhS = 0.0;   // HO: the column's new r* factor and rates
   // ... and the serial thread's d0 of the west and south neighbours: formed before the barrier by
   // two other level slots of the column (other waves) and handed over in the first two rows of
-  // sPh, which nothing else touches until the serial part (Nr >= 2; else the serial thread forms them)
-  const bool hoStash = HO && Nr >= 2 && KW_ >= 4;
+  // sPh, which nothing else touches until the serial part (Nr >= 2, phi_pipe_ok; KW_ >= 4, launch_rstar_exch_phi)
   auto hoD0 = [&](long r) {
     double fc_ = 0.0, c_ = 0.0, w_ = 0.0, s_ = 0.0;
-    if constexpr (HO) r_star_next_point<false>(d, p, f, srcOf, r, fromX, fc_, c_, w_, s_);
+    if constexpr (HO) r_star_next_point<false>(d, p, f, rec, r, fromX, fc_, c_, w_, s_);
     return c_ * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
   };
+  // HO: the level-1 offsets of the three columns u and v are read at
+  long hoC = 0, hoE = 0, hoN = 0;
+  if constexpr (HO) {
+    if (valid && qh) {
+      hoC = mg_at_source3(d, rec, i, j, t);
+      hoE = mg_at_source3(d, rec, i + 1, j, t);
+      hoN = mg_at_source3(d, rec, i, j + 1, t);
+    }
+  }
   // (HO: the column's factor and rates are formed inside the first level's pass, after that
   // level's own loads are issued, so that the two latency chains overlap)
   bool hoHave = false;
@@ -169,9 +183,10 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
     double a = f.rhoInSitu[q3];
     if (qh) {
       const double scalingFactor = p.rhoConst * p.gravitySign * (1.0 / p.gravity);
-      const long qc = HO ? mg_at_source3(d, srcOf, i, j, k, t) : q3;
-      const long qe = HO ? mg_at_source3(d, srcOf, i + 1, j, k, t) : MG_I3(d, i + 1, j, k, t);
-      const long qn = HO ? mg_at_source3(d, srcOf, i, j + 1, k, t) : MG_I3(d, i, j + 1, k, t);
+      const long lvl = (long)(k - 1) * d.n2;
+      const long qc = HO ? hoC + lvl : q3;
+      const long qe = HO ? hoE + lvl : MG_I3(d, i + 1, j, k, t);
+      const long qn = HO ? hoN + lvl : MG_I3(d, i, j + 1, k, t);
       const double u0 = f.uVel[qc], u1 = f.uVel[qe];
       const double v0 = f.vVel[qc], v1 = f.vVel[qn];
       double gW = 0.0;
@@ -185,7 +200,7 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
     if (rstar) {
       if constexpr (HO) {
         if (!hoHave) {
-          r_star_next_point<true>(d, p, f, srcOf, q2, fromX, hoFacC, hoDhC, hoDhW, hoDhS);
+          r_star_next_point<true>(d, p, f, rec, q2, fromX, hoFacC, hoDhC, hoDhW, hoDhS);
           hoHave = true;
         }
         sC[me] = hoDhC * hoOp[0] * hoOp[1] * hoOp[2];
@@ -204,19 +219,17 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
     }
   }
   if constexpr (HO) {
-    if (valid && rstar) {
-      if (!hoHave && kk == 0) r_star_next_point<true>(d, p, f, srcOf, q2, fromX, hoFacC, hoDhC, hoDhW, hoDhS);
-      if (hoStash && ring) {
-        if (kk == KW_ / 4) sPh[cc] = hoD0(q2 - 1);
-        if (kk == KW_ / 2) sPh[NC_ + cc] = hoD0(q2 - d.nx);
-      }
+    // (the serial thread, kk = 0, staged level 1 above: it has the column's factor and rates)
+    if (valid && rstar && ring && (kk == KW_ / 4 || kk == KW_ / 2)) {
+      const bool west = kk == KW_ / 4;
+      sPh[west ? cc : NC_ + cc] = hoD0(west ? q2 - 1 : q2 - d.nx);
     }
   }
   __syncthreads();
   if (valid && kk == 0) {
     double hoW = 0.0, hoS = 0.0;
     if constexpr (HO) {
-      if (rstar && hoStash && ring) { hoW = sPh[cc]; hoS = sPh[NC_ + cc]; }
+      if (rstar && ring) { hoW = sPh[cc]; hoS = sPh[NC_ + cc]; }
     }
     double phF = 0.0;
     for (int k2 = 1; k2 <= Nr; k2++) {
@@ -229,8 +242,7 @@ __device__ __forceinline__ void phi_hyd_body(const Dims &d, const Params &p, con
       auto d0 = [&](long r) {
         if constexpr (HO) {
           if (r == q2) return hoDhC * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
-          if (hoStash) return r == q2 - 1 ? hoW : hoS;
-          return hoD0(r);
+          return r == q2 - 1 ? hoW : hoS;
         } else {
           return f.rStarDhCDt[r] * (f.Ro_surf[r] - f.R_low[r]) * f.rA[r];
         }

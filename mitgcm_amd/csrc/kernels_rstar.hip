@@ -72,24 +72,31 @@ __global__ void __launch_bounds__(256) k_rstar_exmix(Dims d, Params p, Fields f,
 // PH = 2 (MG_FUSE_PHIP): also keeps the factors it read in rStarFac{C,W,S}Prev, each column its
 // own point -- the old factors of this step's CALC_R_STAR, for the next step's CALC_PHI_HYD riding
 // in CALC_R_STAR's grid (rstar.h r_star_next_point)
-template <bool SFP, int PH>
+// O (common.h): the option set the riders and the column frame are compiled for.  The pinned
+// instantiation is the pipelined step's launch: the operator and the preconditioner were built
+// beside DYNAMICS (opIn = 0, nbPc = 0; launch_update_r_star_cg2d refuses it anything else), so
+// neither the operator's sums nor ucg2d_p_point are compiled into it
+template <bool SFP, int PH, class O = OptsRun>
 __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, Fields f, int nc, int opIn,
                                                               const long *__restrict__ srcOf, int nbPc,
                                                               const int *iterPtr, int nbPh) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   int lb = mg_xcd_block();
   if constexpr (PH != 0) {
-    if (lb < nbPh) { phys_hoist_body(d, p, f, iterPtr, srcOf, lb); return; }
+    if (lb < nbPh) { phys_hoist_body<O>(d, p, f, iterPtr, srcOf, lb); return; }
     lb -= nbPh;
   }
-  if (lb < nbPc) { ucg2d_p_point(d, p, f, srcOf, lb); return; }
-  lb -= nbPc;
+  if constexpr (!O::pinned) {
+    if (lb < nbPc) { ucg2d_p_point(d, p, f, srcOf, lb); return; }
+    lb -= nbPc;
+  }
   MG_COLF_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, nc, lb)
   const int NS = d.Nr * NC_;
   double *sW = lds, *sS = lds + NS;
   double *fE = lds + 2 * NS, *fW = lds + 3 * NS, *fN = lds + 4 * NS, *fS = lds + 5 * NS;   // SFP only
   const long q = MG_I2(d, i, j, t);
-  const bool op = opIn && p.nonlinFreeSurf > 2 && i >= 1 && i <= d.sNx + 1 && j >= 1 && j <= d.sNy + 1;
+  const bool opAny = !O::pinned && opIn && O::opEveryStep(p);
+  const bool op = opAny && i >= 1 && i <= d.sNx + 1 && j >= 1 && j <= d.sNy + 1;
   const bool inner = i >= 1 && i <= d.sNx && j >= 1 && j <= d.sNy;
   if (valid) {
     const double fc = f.rStarFacC[q], fw = f.rStarFacW[q], fs = f.rStarFacS[q];
@@ -115,7 +122,7 @@ __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, 
         sS[me] = faceArea * f.recip_dyC[q];
       }
       if (SFP) {
-        if (p.useCDscheme) {
+        if (O::cdScheme(p)) {
           f.uNM1[q3] = f.uVel[q3];
           f.vNM1[q3] = f.vVel[q3];
         }
@@ -132,7 +139,7 @@ __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, 
   }
   __syncthreads();
   if (!valid || kk != 0) return;
-  if (opIn && p.nonlinFreeSurf > 2) {
+  if (opAny) {
     double aW = 0.0, aS = 0.0;
     if (op) {
       for (int k = 1; k <= d.Nr; k++) {
@@ -146,7 +153,7 @@ __global__ void __launch_bounds__(256) k_update_r_star_cg2d_a(Dims d, Params p, 
     f.aW2d[q] = aW;
     f.aS2d[q] = aS;
   }
-  if (SFP) sfp_rhs_column(d, p, f, q, inner, fE, fW, fN, fS, NC_, cc);
+  if (SFP) sfp_rhs_column<O>(d, p, f, q, inner, fE, fW, fN, fS, NC_, cc);
 }
 
 // UPDATE_CG2D part 2 (ucg2d.h ucg2d_p_point)
@@ -194,8 +201,10 @@ hipError_t launch_rstar_exmix(const Dims &d, const Params &p, const Fields &f, c
 // pcHere (with opEarly): only the operator was, the preconditioner rides in this launch
 // iterPtr non-null: the next step's DO_OCEANIC_PHYS rides at the head of the grid; keepFac with it:
 // the factors are also kept in rStarFac*Prev
+// spec (StepPlan::spec2): the instantiation compiled for the pinned option set (common.h OptsGO90),
+// which exists for the pipelined step's launch only: sfp, opEarly without pcHere, iterPtr, keepFac
 hipError_t launch_update_r_star_cg2d(const Dims &d, const Params &p, const Fields &f, const long *srcOf, hipStream_t s,
-                                     bool sfp, bool opEarly, bool pcHere, const int *iterPtr, bool keepFac) {
+                                     bool sfp, bool opEarly, bool pcHere, const int *iterPtr, bool keepFac, bool spec) {
   const long n = d.n2 * d.nTiles;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const long ncol = (long)d.nx * d.ny * d.nT;
@@ -206,12 +215,15 @@ hipError_t launch_update_r_star_cg2d(const Dims &d, const Params &p, const Field
   MG_ALLOW_LDS(kPlain);
   MG_ALLOW_LDS(kSfp);
   const int nbPc = (opEarly && pcHere && p.nonlinFreeSurf > 2) ? (int)nb : 0;
+  if (spec && !(sfp && opEarly && !pcHere && iterPtr && keepFac && opts_match(p))) return hipErrorInvalidValue;
   if (iterPtr) {
     if (!sfp) return hipErrorInvalidValue;   // (one_step pipelines only the fused right-hand side's layout)
     MG_ALLOW_LDS(kSfpPhys);
     MG_ALLOW_LDS(kSfpPhysKeep);
     const int nbPh = phys_hoist_blocks(d);
-    hipLaunchKernelGGL(keepFac ? kSfpPhysKeep : kSfpPhys, dim3(mg_colf_blocks(ncol, nc) + (unsigned)(nbPc + nbPh)), dim3(256),
+    auto kPinned = k_update_r_star_cg2d_a<true, 2, OptsGO90>;
+    MG_ALLOW_LDS(kPinned);
+    hipLaunchKernelGGL(spec ? kPinned : keepFac ? kSfpPhysKeep : kSfpPhys, dim3(mg_colf_blocks(ncol, nc) + (unsigned)(nbPc + nbPh)), dim3(256),
                        mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, nc, opEarly ? 0 : 1, srcOf, nbPc, iterPtr, nbPh);
   } else if (keepFac) {
     return hipErrorInvalidValue;

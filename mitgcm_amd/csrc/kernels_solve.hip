@@ -1094,13 +1094,17 @@ __global__ void __launch_bounds__(256) k_exch_etaH(Dims d, Params p, Fields f, c
 // GM (MG_FUSE_PIPE): the next step's GMREDI_CALC_TENSOR on the first nbGm logical blocks
 // (gm_tensor.h; it reads the rhoInSitu and sigmaR that step's DO_OCEANIC_PHYS left earlier in
 // this step, and writes the tensor, which nothing else in this step reads any more)
-template <bool GM>
-__global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, int atInit, int nc,
+// O (common.h): the option set the tensor and the column frame are compiled for.  The pinned
+// instantiation is the step's call (atInit = 0 with etaSrc; launch_corr_cont refuses it anything
+// else), so the initialisation's and the routine-level forms are not compiled into it
+template <bool GM, class O = OptsRun>
+__global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, int atInitIn, int nc,
                                                    const long *__restrict__ etaSrc, int nbGm) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int atInit = O::pinned ? 0 : atInitIn;
   int lb = mg_xcd_block();
   if constexpr (GM) {
-    if (lb < nbGm) { gm_tensor_body(d, p, f, lb); return; }
+    if (lb < nbGm) { gm_tensor_body<O>(d, p, f, lb); return; }
     lb -= nbGm;
   }
   MG_COLF_LB(1, d.sNx, 1, d.sNy, nc, lb)
@@ -1108,7 +1112,7 @@ __global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, i
   // sH0 (r* only) last: launch_corr_cont allocates it only under r*
   double *sDiv = lds, *sMask = lds + NS, *sU = lds + 2 * NS, *sV = lds + 3 * NS, *sH0 = lds + 4 * NS;
   const long q = MG_I2(d, i, j, t);
-  const bool rstar = p.nonlinFreeSurf > 0 && p.select_rStar != 0;
+  const bool rstar = O::pinned || (p.nonlinFreeSurf > 0 && p.select_rStar != 0);   // (pinned: O::rstar)
   if (valid && atInit != 0) MG_COLF_K(k) {   // divergence of the velocities already in uVel, vVel
     const int me = (k - 1) * NC_ + cc;
     const double drF = f.drF[k - 1];
@@ -1124,7 +1128,7 @@ __global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, i
   } else if (valid) {
     const double psFac = p.pfFacMom * p.implicSurfPress;
     auto eta = [&](long qq) {
-      if (!etaSrc) return f.etaN[qq];
+      if (!O::pinned && !etaSrc) return f.etaN[qq];
       const long sq = etaSrc[qq];
       return f.recip_Bo[qq] * f.cg2d_x[sq >= 0 ? sq : qq];
     };
@@ -1170,11 +1174,11 @@ __global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, i
   __syncthreads();
   if (valid && kk == 0) {
     double rStarDhDt = 0.0;
-    if (p.exactConserv) {
+    if (O::exactConserv(p)) {
       double hDiv = 0.0;
       for (int k2 = 1; k2 <= d.Nr; k2++) hDiv = hDiv + sMask[(k2 - 1) * NC_ + cc] * sDiv[(k2 - 1) * NC_ + cc];
       double dEtaHdt;
-      if (atInit == 1 && p.nIter0 != 0 && p.useRealFreshWaterFlux) {
+      if (atInit == 1 && p.nIter0 != 0 && O::realFreshWaterFlux(p)) {
         // integr_continuity.F:117-136: PmEpR consistent with the pickup's dEtaHdt
         dEtaHdt = f.dEtaHdt[q];
         double pm = dEtaHdt + hDiv * f.recip_rA[q];
@@ -1185,7 +1189,7 @@ __global__ void __launch_bounds__(256) k_corr_cont(Dims d, Params p, Fields f, i
         if (f.PmEpR) f.PmEpR[q] = 0.0;
         f.cg2d_b[q] = f.etaN[q];
       } else {
-        const double facEmP = p.useRealFreshWaterFlux ? 1.0 / p.rhoConst : 0.0;   // integr_continuity.F:183-188
+        const double facEmP = O::realFreshWaterFlux(p) ? 1.0 / p.rhoConst : 0.0;   // integr_continuity.F:183-188
         dEtaHdt = -(hDiv * f.recip_rA[q]) - facEmP * f.EmPmR[q];
         f.cg2d_b[q] = f.etaH[q] + p.implicDiv2DFlow * dEtaHdt * p.deltaTFreeSurf;
       }
@@ -1514,8 +1518,11 @@ hipError_t launch_exch_eta(const Dims &d, const Params &p, const Fields &f, cons
 }
 
 // gmNext: the next step's GMREDI_CALC_TENSOR rides at the head of the grid (the column frame only)
+// spec (StepPlan::spec2, with gmNext): the instantiation compiled for the pinned option set (common.h
+// OptsGO90), which exists for the step's call only: atInit = 0 with etaSrc
 hipError_t launch_corr_cont(const Dims &d, const Params &p, const Fields &f, int atInit, hipStream_t s,
-                            const long *etaSrc, bool gmNext) {
+                            const long *etaSrc, bool gmNext, bool spec) {
+  if (spec && !(gmNext && atInit == 0 && etaSrc && opts_match(p))) return hipErrorInvalidValue;
   const long ncol = (long)d.sNx * d.sNy * d.nT;
   const int nArr = (p.nonlinFreeSurf > 0 && p.select_rStar != 0) ? 5 : 4;   // sH0 under r* only
   // deep grids: 32 columns per workgroup (LLC-90: 123 us against 140 at 16,
@@ -1536,8 +1543,10 @@ hipError_t launch_corr_cont(const Dims &d, const Params &p, const Fields &f, int
   // sums and LDS round trips, not by the width of its loads; removed in round 5)
   if (gmNext) {
     const int nbGm = (int)mg_plane_blocks(d.nx - 2, d.ny - 2, d.nT * d.Nr);
-    MG_ALLOW_LDS(k_corr_cont<true>);
-    hipLaunchKernelGGL(k_corr_cont<true>, dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbGm), dim3(256),
+    auto kGen = k_corr_cont<true>, kPinned = k_corr_cont<true, OptsGO90>;
+    MG_ALLOW_LDS(kGen);
+    MG_ALLOW_LDS(kPinned);
+    hipLaunchKernelGGL(spec ? kPinned : kGen, dim3(mg_colf_blocks(ncol, nc) + (unsigned)nbGm), dim3(256),
                        mg_colf_lds(d.Nr, nc, nArr), s, d, p, f, atInit, nc, etaSrc, nbGm);
     return hipGetLastError();
   }

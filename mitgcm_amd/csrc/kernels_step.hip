@@ -370,27 +370,29 @@ hipError_t launch_dyn_thermo(const Dims &d, const Params &p, const Fields &f, co
 // correction step left.  So it runs as further logical blocks of that grid, reading u and v at
 // the sources and forming the factors itself (kernels_dyn.hip phi_hyd_body<HO>,
 // del2uv_body<HO>; rstar.h), and step n+1 starts at k_dt_l2.  No block reads a location another
-// block of the grid writes.  Longest body first:
+// block of the grid writes.  Where a value lives, its column's 3-D base and the owner's (i, j) are
+// read from the HaloRec table (common.h; built with the exchange map), not divided out of srcOf
+// by every thread.  Longest body first:
 //   [CALC_PHI_HYD(n+1) column frame | CALC_R_STAR + UPDATE_ETAH | blocking exchanges | del2uv(n+1)]
-__global__ void __launch_bounds__(256) k_rstar_exch_phi(Dims d, Params p, Fields f, const long *__restrict__ srcOf, int nbR,
+__global__ void __launch_bounds__(256) k_rstar_exch_phi(Dims d, Params p, Fields f, const HaloRec *__restrict__ rec, int nbR,
                                                         XFields x, const long *__restrict__ map, int nHalo, int *ctr,
                                                         int nbX, int nzMax, int nbXall, int fromX, int empNext, int nc,
                                                         int nbPhi) {
   int lb = mg_xcd_block();
-  if (lb < nbPhi) { phi_hyd_body<true>(d, p, f, nc, lb, srcOf, fromX); return; }
+  if (lb < nbPhi) { phi_hyd_body<true>(d, p, f, nc, lb, rec, fromX); return; }
   lb -= nbPhi;
-  if (lb < nbR) { calc_r_star_body<true>(d, p, f, srcOf, lb, fromX, empNext); return; }
+  if (lb < nbR) { calc_r_star_body<true, true>(d, p, f, nullptr, lb, fromX, empNext, rec); return; }
   lb -= nbR;
   if (lb < nbXall) { exchange_multi_body(d, x, map, nHalo, ctr, lb % nbX, (lb / nbX) % nzMax, lb / (nbX * nzMax)); return; }
-  del2uv_body<true>(d, p, f, lb - nbXall, srcOf);
+  del2uv_body<true>(d, p, f, lb - nbXall, rec);
 }
 
 // where the rider is exact and has its column frame: r* with the column-frame CALC_PHI_HYD in the
 // default layout's first grid (not the flat pass), and MGCM_STEP_FUSE bit MG_FUSE_PHIP
+// (two levels or more: the rider hands values over in two rows of its LDS frame, phi_hyd_body<HO>)
 bool phi_pipe_ok(const Dims &d, const Params &p) {
-  (void)d;
   return mg_fuse_on(MG_FUSE_PHIP) && p.nonlinFreeSurf > 0 && p.select_rStar > 0 && p.exactConserv && !p.cubeCorners &&
-         dyn_thermo_takes_gm(p) && !phi_flat_on(p);
+         dyn_thermo_takes_gm(p) && !phi_flat_on(p) && d.Nr >= 2;
 }
 
 // CALC_PHI_HYD | del2uv stand-alone, for the first step of a pipelined call (k_dt_l1 without the tensor)
@@ -401,9 +403,9 @@ hipError_t launch_phi_del2(const Dims &d, const Params &p, const Fields &f, hipS
 
 // launch_rstar_exch (kernels_rstar.hip) with the next step's CALC_PHI_HYD and del2uv; x is the
 // exchange set without totPhiHyd
-hipError_t launch_rstar_exch_phi(const Dims &d, const Params &p, const Fields &f, const long *srcOf, const XFields &x,
+hipError_t launch_rstar_exch_phi(const Dims &d, const Params &p, const Fields &f, const HaloRec *rec, const XFields &x,
                                  const long *map, int nHalo, int *ctr, hipStream_t s, int fromX, int empNext) {
-  if (!phi_pipe_ok(d, p) || !srcOf || d.nT != d.nTiles) return hipErrorInvalidValue;
+  if (!phi_pipe_ok(d, p) || !rec || d.nT != d.nTiles) return hipErrorInvalidValue;
   const long n = d.n2 * d.nTiles;
   const int nbR = (int)((n + 255) / 256);
   int nzMax = 1;
@@ -412,10 +414,12 @@ hipError_t launch_rstar_exch_phi(const Dims &d, const Params &p, const Fields &f
   const int nbXall = nbX * nzMax * (x.n > 0 ? x.n : 1);
   int nc, nArr, nbPhi;
   phi_frame(d, p, nc, nArr, nbPhi);
+  // (the rider's hand-over is written by the level slots KW_/4 and KW_/2 of a column, phi_hyd_body<HO>)
+  if (256 / nc < 4) return hipErrorInvalidValue;
   const int nbDel = del2_needed(p) ? (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr) : 0;
   MG_ALLOW_LDS(k_rstar_exch_phi);
   hipLaunchKernelGGL(k_rstar_exch_phi, dim3((unsigned)(nbPhi + nbR + nbXall + nbDel)), dim3(256), mg_colf_lds(d.Nr, nc, nArr),
-                     s, d, p, f, srcOf, nbR, x, map, nHalo, ctr, nbX, nzMax, nbXall, fromX, empNext, nc, nbPhi);
+                     s, d, p, f, rec, nbR, x, map, nHalo, ctr, nbX, nzMax, nbXall, fromX, empNext, nc, nbPhi);
   return hipGetLastError();
 }
 

@@ -29,7 +29,7 @@ hipError_t launch_exchange_uv_pairs(const Dims &, double *const *, double *const
 hipError_t launch_exch_eta(const Dims &, const Params &, const Fields &, const long *, bool, int, hipStream_t,
                            int fromX = 0);
 hipError_t launch_corr_cont(const Dims &, const Params &, const Fields &, int, hipStream_t, const long *etaSrc = nullptr,
-                            bool gmNext = false);
+                            bool gmNext = false, bool spec = false);
 hipError_t launch_halo_pack(const Dims &, const XFields &, const long *, long, double *, int, hipStream_t);
 
 // ---- kernels_cg2d_dist.hip
@@ -46,7 +46,7 @@ hipError_t launch_rstar_exch(const Dims &, const Params &, const Fields &, const
                              int, int *, hipStream_t, int fromX = 0, int empNext = 0);
 hipError_t launch_update_r_star_cg2d(const Dims &, const Params &, const Fields &, const long *, hipStream_t, bool sfp = false,
                                      bool opEarly = false, bool pcHere = false, const int *iterPtr = nullptr,
-                                     bool keepFac = false);
+                                     bool keepFac = false, bool spec = false);
 
 // ---- kernels_thermo.hip (through kernels_step.hip)
 bool phys_ring_ok(const Dims &, const Params &, const Fields &);
@@ -64,7 +64,7 @@ hipError_t launch_dyn_thermo(const Dims &, const Params &, const Fields &, const
 bool dyn_thermo_spec_ok(const Params &);
 bool phi_pipe_ok(const Dims &, const Params &);
 hipError_t launch_phi_del2(const Dims &, const Params &, const Fields &, hipStream_t);
-hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, const long *, const XFields &, const long *, int,
+hipError_t launch_rstar_exch_phi(const Dims &, const Params &, const Fields &, const HaloRec *, const XFields &, const long *, int,
                                  int *, hipStream_t, int fromX, int empNext);
 bool dyn_thermo_takes_gm(const Params &);
 bool gm_phi_fusable(const Dims &, const Params &);

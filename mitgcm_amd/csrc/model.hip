@@ -150,6 +150,7 @@ struct mgcm_model {
   // halo map (2*nHalo longs) and CG2D neighbour table
   long *d_halo = nullptr;
   long *d_srcOf = nullptr;    // per 2-D point: interior source of a halo point, -1 otherwise
+  mgcm::HaloRec *d_haloRec = nullptr;   // per 2-D point: srcOf's topology as a record (common.h), or null (no 32-bit fit)
   int nHalo = 0;
   long *d_haloAll = nullptr;  // the map of EVERY tile's halo when this model steps a tile subset
   int nHaloAll = 0;           // (EXCH_*_RL on host arrays, mgcm_exchange_host, covers the domain)
@@ -374,14 +375,54 @@ static void build_latlon_halo(mgcm_model *m) {
   }
 }
 
+// The HaloRec table of an exchange map (common.h): for every 2-D point q of the nTiles tiles, where
+// its value lives (srcOf[q], else q), that offset as the base of a 3-D column, the (i, j) of that
+// owner, and whether q is interior / mapped.  Plain host code (mgcm_halo_table reaches it without
+// a device).  Returns -1, out untouched, where an offset does not fit its 32-bit field.
+namespace mgcm {
+int mg_build_halo_table(const Dims &d, const long *srcOf, HaloRec *out) {
+  if (d.n3 * d.nTiles >= (1L << 31) || d.nx + d.OLx >= (1 << 15) || d.ny + d.OLy >= (1 << 15)) return -1;
+  const long N2 = d.n2 * d.nTiles;
+  for (long q = 0; q < N2; q++) {
+    const long sq = srcOf[q], at = sq >= 0 ? sq : q;
+    int i, j, iq, jq;
+    mg_ij_of(d, at, i, j);
+    mg_ij_of(d, q, iq, jq);
+    HaloRec h;
+    h.at2 = (int)at;
+    h.base3 = (int)((at / d.n2) * d.n3 + at % d.n2);
+    h.i = (short)i;
+    h.j = (short)j;
+    h.flags = ((iq >= 1 && iq <= d.sNx && jq >= 1 && jq <= d.sNy) ? MG_HR_INTERIOR : 0) | (sq >= 0 ? MG_HR_MAPPED : 0);
+    out[q] = h;
+  }
+  return 0;
+}
+}  // namespace mgcm
+int mgcm_halo_table(int sNx, int sNy, int OLx, int OLy, int Nr, int nTiles, const long *srcOf, int *out) {
+  mgcm::Dims d{};
+  d.sNx = sNx; d.sNy = sNy; d.OLx = OLx; d.OLy = OLy; d.Nr = Nr; d.nTiles = nTiles; d.nT = nTiles;
+  d.nx = sNx + 2 * OLx; d.ny = sNy + 2 * OLy; d.n2 = (long)d.nx * d.ny; d.n3 = d.n2 * Nr;
+  static_assert(sizeof(mgcm::HaloRec) == 4 * sizeof(int), "a HaloRec is four ints to the caller");
+  return mgcm::mg_build_halo_table(d, srcOf, reinterpret_cast<mgcm::HaloRec *>(out));
+}
+
 static int upload_halo(mgcm_model *m) {
   if (m->d_halo) { hipFree(m->d_halo); m->d_halo = nullptr; }
   if (m->d_srcOf) { hipFree(m->d_srcOf); m->d_srcOf = nullptr; }
+  if (m->d_haloRec) { hipFree(m->d_haloRec); m->d_haloRec = nullptr; }
   const long N2 = m->d.n2 * m->d.nTiles;
   std::vector<long> srcOf(N2, -1);
   for (size_t h = 0; h + 1 < m->h_halo.size(); h += 2) srcOf[m->h_halo[h]] = m->h_halo[h + 1];
   HIPCHK(hipMalloc(&m->d_srcOf, N2 * sizeof(long)));
   HIPCHK(hipMemcpy(m->d_srcOf, srcOf.data(), N2 * sizeof(long), hipMemcpyHostToDevice));
+  // ... and the same map as records, for the end-of-step grid's riders (k_rstar_exch_phi); without
+  // them (no 32-bit fit) plan_step keeps the plain end of step (StepPlan::phiPipeOk)
+  std::vector<mgcm::HaloRec> rec(N2);
+  if (mgcm::mg_build_halo_table(m->d, srcOf.data(), rec.data()) == 0) {
+    HIPCHK(hipMalloc(&m->d_haloRec, N2 * sizeof(mgcm::HaloRec)));
+    HIPCHK(hipMemcpy(m->d_haloRec, rec.data(), N2 * sizeof(mgcm::HaloRec), hipMemcpyHostToDevice));
+  }
   // the 3-D exchange kernels refresh the halos of this process's tiles only
   // (tile-sharded runs receive the remote sources first, mgcm_halo_unpack)
   std::vector<long> loc;
@@ -1009,6 +1050,7 @@ void mgcm_destroy(mgcm_model *m) {
   if (m->monBuf) hipFree(m->monBuf);
   if (m->d_halo) hipFree(m->d_halo);
   if (m->d_srcOf) hipFree(m->d_srcOf);
+  if (m->d_haloRec) hipFree(m->d_haloRec);
   if (m->d_haloAll) hipFree(m->d_haloAll);
   for (int q = 0; q < 2; q++) {
     if (m->d_uv[q]) hipFree(m->d_uv[q]);
@@ -1419,9 +1461,9 @@ static hipError_t calc_r_star(mgcm_model *m, bool fuseEtaH = false, int fromX = 
 // sfp: k_sfp_rhs fused into the r* column pass (FORWARD_STEP on the whole domain only: in a
 // tile-sharded run the r* pass covers every tile and the right-hand side this process's own)
 static hipError_t update_r_star_cg2d(mgcm_model *m, bool sfp = false, bool opEarly = false, bool pcHere = false,
-                                     const int *physNext = nullptr, bool keepFac = false) {
+                                     const int *physNext = nullptr, bool keepFac = false, bool spec = false) {
   return launch_update_r_star_cg2d(all_tiles(m->d), m->p, m->f, m->d_srcOf, m->stream, sfp, opEarly, pcHere, physNext,
-                                   keepFac);
+                                   keepFac, spec);
 }
 
 int mgcm_init(mgcm_model *m) {
@@ -2174,6 +2216,11 @@ struct StepPlan {
   // set (common.h OptsGO90, MG_FUSE_SPEC): the model's options are that set and the fold's default
   // layout runs (dyn_thermo_spec_ok).  A choice of instantiation only: the same launches, the same bits
   bool spec;
+  // ... and so do, in a pipelined call, the two grids on either side of the pressure solve: the
+  // r* column pass with the next step's DO_OCEANIC_PHYS and the correction step with the next
+  // step's tensor (MG_FUSE_SPEC2; the instantiations that exist are those of the hoisting step with
+  // the operator built early and CALC_PHI_HYD pipelined as well)
+  bool spec2;
 };
 static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   const Params &p = m->p;
@@ -2215,13 +2262,14 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
   pl.resFlowFold = pl.resFlow && pl.dtFused;
   pl.pipeOk = gmFold && pl.sfpFused && pl.endFused && mg_fuse_on(MG_FUSE_PIPE) && p.select_rStar > 0 &&
               p.useRealFreshWaterFlux && p.exactConserv && m->d_srcOf && !totPhiHalo && !pl.resFlow;
-  pl.phiPipeOk = pl.pipeOk && phi_pipe_ok(d, p);
+  pl.phiPipeOk = pl.pipeOk && phi_pipe_ok(d, p) && m->d_haloRec;
   pl.pipe = mode != STEP_PLAIN;
   pl.hoist = mode == STEP_HOIST;
   pl.valid = !pl.pipe || pl.pipeOk;
   pl.phiPipe = pl.pipe && pl.phiPipeOk;
   pl.phiNext = pl.hoist && pl.phiPipe;
   pl.empNext = pl.hoist && p.periodicExternalForcing;
+  pl.spec2 = pl.spec && pl.phiPipe && pl.opEarly && pl.etaX && mg_fuse_on(MG_FUSE_SPEC2);
   // (a pipelined step's DO_OCEANIC_PHYS ran in the previous step's grids, or at the head of the call)
   pl.ringPhys = !pl.pipe && !pl.ringAside && ringSep && mg_fuse_on(MG_FUSE_RINGP) && phys_ring_ok(d, p, m->f);
   pl.momRing = !pl.ringAside && !pl.ringPhys;
@@ -2230,11 +2278,12 @@ static StepPlan plan_step(const mgcm_model *m, StepMode mode) {
 // mgcm_get_param("stepLayout") (model.py step_layout): bit 0 THERMODYNAMICS folded into
 // DYNAMICS' grids (k_dt_l1/l2/l3), 2 the tracers on the second stream, 3 joined only before the
 // correction step, 4 pipelined, 5 with the next step's CALC_PHI_HYD too, 6 (value 64) the fold's
-// bodies compiled for the pinned option set; bit 1 is retired
+// bodies compiled for the pinned option set, 7 (value 128) the pipelined call's r* and
+// correction-step grids too; bit 1 is retired
 // (the graph's layout: the eager timed pass, one stream, serialises a fork it reports here)
 static int step_layout_bits(const StepPlan &pl) {
   return (pl.dtFused ? 1 : 0) | (pl.forkable && !pl.dtFused ? 4 : 0) | (pl.forkable && pl.forkLate ? 8 : 0) |
-         (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0) | (pl.spec ? 64 : 0);
+         (pl.pipe ? 16 : 0) | (pl.phiPipe ? 32 : 0) | (pl.spec ? 64 : 0) | (pl.spec2 ? 128 : 0);
 }
 
 // THERMODYNAMICS onto the second stream (after the model stream's work so far), evJoin behind
@@ -2281,16 +2330,18 @@ static int one_step(mgcm_model *m, StepMode mode = STEP_PLAIN) {
     } else if (dynamics_on(m, pl.momRing)) return -1;
     if (pl.forkEarly) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
     if (pl.rstar)
-      TIMED(K_RSTAR, update_r_star_cg2d(m, pl.sfpFused, pl.opEarly, false, pl.hoist ? m->d_ctr : nullptr, pl.phiNext));
+      TIMED(K_RSTAR, update_r_star_cg2d(m, pl.sfpFused, pl.opEarly, false, pl.hoist ? m->d_ctr : nullptr, pl.phiNext,
+                                        pl.spec2 && pl.hoist));
     if (!pl.sfpFused) TIMED(K_RHS, launch_sfp_rhs(m->d, m->p, m->f, m->stream));
     if (pl.thermoLate && fork_thermo(m, pl.ringAside, pl.trEx)) return -1;
     TIMED(K_CG2D, launch_cg2d(m, m->p.cg2dMaxIters, m->p.cg2dUseMinResSol - 1));
     if (!pl.etaX) TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, false, 0, m->stream));
     if (pl.thermoLate) HIPCHK(hipStreamWaitEvent(m->stream, m->evJoin, 0));
-    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, pl.etaX ? m->d_srcOf : nullptr, pl.hoist));
+    TIMED(K_CONT, launch_corr_cont(m->d, m->p, m->f, 0, m->stream, pl.etaX ? m->d_srcOf : nullptr, pl.hoist,
+                                   pl.spec2 && pl.hoist));
     if (pl.etaHAlone) TIMED(K_ETA, launch_exch_eta(m->d, m->p, m->f, m->d_srcOf, true, 0, m->stream, fromX));
     if (pl.endFused && pl.phiNext)
-      TIMED(K_RSTAR, launch_rstar_exch_phi(m->d, m->p, m->f, m->d_srcOf, blocking_fields(m, 1, false), m->d_halo, m->nHalo,
+      TIMED(K_RSTAR, launch_rstar_exch_phi(m->d, m->p, m->f, m->d_haloRec, blocking_fields(m, 1, false), m->d_halo, m->nHalo,
                                            m->d_ctr, m->stream, fromX, pl.empNext ? 1 : 0));
     else if (pl.endFused)
       TIMED(K_RSTAR, launch_rstar_exch(m->d, m->p, m->f, m->d_srcOf, pl.fuseEtaH, blocking_fields(m), m->d_halo, m->nHalo,

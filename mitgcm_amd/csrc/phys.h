@@ -34,13 +34,15 @@ __device__ __forceinline__ double jmd95_rho(const Params &p, double locPres, dou
 // PRESSURE_FOR_EOS (pressure_for_eos.F:51-105), z-coordinates, dpRef = 0: JMD95P
 // (selectP_inEOS_Zc = 2) uses the hydrostatic pressure rhoConst*(totPhiHyd + phiRef(2k))
 // of the point q3 (level kRef); JMD95Z the reference profile pRef4EOS(kRef).
+template <class O = OptsRun>
 __device__ __forceinline__ double pressure_for_eos(const Params &p, const Fields &f, int kRef, long q3) {
-  if (p.selectP_inEOS_Zc == 2) return p.rhoConst * (f.totPhiHyd[q3] + f.phiRefC[kRef - 1]) + 0.0;
+  if (O::eosPresFromPhi(p)) return p.rhoConst * (f.totPhiHyd[q3] + f.phiRefC[kRef - 1]) + 0.0;
   return f.pRef4EOS[kRef - 1] + 0.0;
 }
 // q3: flat offset of the point at level kRef (for the JMD95P pressure)
+template <class O = OptsRun>
 __device__ __forceinline__ double find_rho(const Params &p, const Fields &f, int kRef, long q3, double t, double s) {
-  if (p.eosType == 1) return jmd95_rho(p, pressure_for_eos(p, f, kRef, q3), t, s);
+  if (O::eosJmd95(p)) return jmd95_rho(p, pressure_for_eos<O>(p, f, kRef, q3), t, s);
   const double refTemp = f.tRef[kRef - 1], refSalt = f.sRef[kRef - 1];
   const double dRho = p.rhoNil - p.rhoConst;
   return p.rhoNil * (p.sBeta * (s - refSalt) - p.tAlpha * (t - refTemp)) + dRho;
@@ -76,7 +78,8 @@ __device__ __forceinline__ double find_rho(const Params &p, const Fields &f, int
 //     then copies the clamped value into the images, as it finds them after today's pass.  (A
 //     thread of an image may read its source before or after the owner's store; both clamp to
 //     the same value.)
-template <bool HOIST>
+// O: the option set the point is compiled for (common.h; OptsGO90 in the pinned UPDATE_R_STAR grid)
+template <bool HOIST, class O = OptsRun>
 __device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
                                                        const long *__restrict__ srcOf, int i, int j, int k, int t) {
   const long q = MG_I2(d, i, j, t), q31 = MG_I3(d, i, j, 1, t);
@@ -89,9 +92,9 @@ __device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Para
   }
   auto theta_at = [&](int kk) {
     const double v = f.theta[HOIST ? r31 + (long)(kk - 1) * d.n2 : MG_I3(d, i, j, kk, t)];
-    return (kk == 1 && p.allowFreezing && v < -1.9) ? -1.9 : v;
+    return (kk == 1 && O::allowFreezing(p) && v < -1.9) ? -1.9 : v;
   };
-  if (k == 1 && p.periodicExternalForcing) {
+  if (k == 1 && O::periodicForcing(p)) {
     const long N2 = d.n2 * d.nTiles;
     const double cycleLength = p.externForcingCycle, recSpacing = p.externForcingPeriod;
     const double currentTime = (double)(*iterPtr + (HOIST ? 1 : 0)) * p.deltaTClock;
@@ -111,7 +114,7 @@ __device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Para
   }
   if (k == 1) {
     const double th1 = theta_at(1), s1 = f.salt[HOIST ? r31 : q31];
-    if (p.allowFreezing && own) f.theta[q31] = th1;
+    if (O::allowFreezing(p) && own) f.theta[q31] = th1;
     const double mass2rUnit = 1.0 / p.rhoConst, recip_Cp = 1.0 / p.HeatCapacity_Cp;
     const double hFac1 = HOIST ? f.h0FacC[q31] * f.rStarFacC[q] : f.hFacC[q31];
     double sfT = -(f.lambdaThetaClimRelax[q] * (th1 - f.SST[q]) * f.drF[0] * hFac1);
@@ -119,7 +122,7 @@ __device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Para
     sfT = sfT - f.Qnet[q] * recip_Cp * mass2rUnit;
     sfS = sfS - 0.0 * mass2rUnit;   // saltFlux = 0
     const double UNSET_RL = 123456.7;
-    if (p.nonlinFreeSurf > 0 && p.useRealFreshWaterFlux) {
+    if (O::nlfs0(p) && O::realFreshWaterFlux(p)) {
       // external_forcing_surf.F:253-277: PmEpR changes the column height
       const double pmepr = HOIST ? -f.EmPmR[q] : f.PmEpR[q];
       if (p.temp_EvPrRn != UNSET_RL) sfT = sfT + pmepr * (p.temp_EvPrRn - th1) * mass2rUnit;
@@ -136,18 +139,18 @@ __device__ __forceinline__ double oceanic_phys_point_t(const Dims &d, const Para
   }
   const long q3 = MG_I3(d, i, j, k, t);
   const long r3 = HOIST ? r31 + (long)(k - 1) * d.n2 : q3;   // where theta, salt and totPhiHyd are read
-  const double rho = find_rho(p, f, k, r3, theta_at(k), f.salt[r3]);
+  const double rho = find_rho<O>(p, f, k, r3, theta_at(k), f.salt[r3]);
   f.rhoInSitu[q3] = rho;
-  const bool calcConvect = p.ivdc_kappa != 0.0;
+  const bool calcConvect = O::ivdc(p);
   double conv = 0.0, sigmaR = 0.0;
-  if (k >= 2 && (calcConvect || p.useGMRedi)) {
+  if (k >= 2 && (calcConvect || O::gmRedi(p))) {
     const long q3u = MG_I3(d, i, j, k - 1, t);
-    const double rhoKm1 = find_rho(p, f, k, r3, theta_at(k - 1), f.salt[r3 - d.n2]);
+    const double rhoKm1 = find_rho<O>(p, f, k, r3, theta_at(k - 1), f.salt[r3 - d.n2]);
     sigmaR = f.maskC[q3] * f.maskC[q3u] * f.recip_drC[k - 1] * p.rkSign * (rho - rhoKm1);
     if (calcConvect) conv = (-sigmaR * p.gravitySign > 0.0) ? 1.0 : 0.0;
   }
   f.IVDConvCount[q3] = conv;
-  if (p.useGMRedi) f.sigmaR[q3] = sigmaR;
+  if (O::gmRedi(p)) f.sigmaR[q3] = sigmaR;
   return rho;
 }
 __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
@@ -156,11 +159,12 @@ __device__ __forceinline__ double oceanic_phys_point(const Dims &d, const Params
 }
 // the next step's pass on the logical blocks of another kernel's grid: k_oceanic_phys's frame
 // (one thread per (i,j,k) of the full halo range, phys_hoist_blocks blocks)
+template <class O = OptsRun>
 __device__ __forceinline__ void phys_hoist_body(const Dims &d, const Params &p, const Fields &f, const int *iterPtr,
                                                 const long *__restrict__ srcOf, int lb) {
   MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
-  oceanic_phys_point_t<true>(d, p, f, iterPtr, srcOf, i, j, k, t);
+  oceanic_phys_point_t<true, O>(d, p, f, iterPtr, srcOf, i, j, k, t);
 }
 inline int phys_hoist_blocks(const Dims &d) { return (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr); }
 

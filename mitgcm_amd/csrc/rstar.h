@@ -25,51 +25,37 @@ __device__ __forceinline__ double eta_exch(const Dims &d, const Fields &f, const
   return fromX ? f.recip_Bo[q] * f.cg2d_x[q] : f.etaN[q];
 }
 
-// (i, j) of the 2-D offset q.  NARROW: in 32-bit arithmetic (grids of fewer than 2^31 2-D points)
-template <bool NARROW>
-__device__ __forceinline__ void mg_ij_of(const Dims &d, long q, int &i, int &j) {
-  if constexpr (NARROW) {
-    const int l = (int)q % (int)d.n2;
-    i = l % d.nx - d.OLx + 1;
-    j = l / d.nx - d.OLy + 1;
-  } else {
-    const long l = q % d.n2;
-    i = (int)(l % d.nx) - d.OLx + 1;
-    j = (int)(l / d.nx) - d.OLy + 1;
-  }
-}
-
 // The new factors fc, fw, fs of point q from the old ones oc, ow, os (kept where the point's
 // source lies outside the reference's ranges).  WS = false: the centre factor only.
-// SHORT (the rider in CALC_R_STAR's own grid, rstar.h r_star_next_point; EXCH1 topologies, FUSE):
-// the same values through shorter address chains -- an interior point is nobody's image, so it is
-// its own source and its eta is cg2d_b there, without the look-ups in srcOf; 32-bit index
-// arithmetic.  The expressions that form the factors are the ones below for both.
+// SHORT (k_rstar_exch_phi's grid: its own CALC_R_STAR blocks and the rider, r_star_next_point;
+// EXCH1 topologies, FUSE): the same values through shorter address chains -- where the value is
+// computed and its (i, j) come from the point's HaloRec (one load, no division), and an interior
+// point is nobody's image, so its eta is cg2d_b there without a look-up.  The expressions that
+// form the factors are the ones below for both.
 template <bool FUSE, bool WS = true, bool SHORT = false>
 __device__ __forceinline__ void calc_r_star_fac(const Dims &d, const Params &p, const Fields &f,
-                                                const long *__restrict__ srcOf, long q, int fromX, double oc, double ow,
-                                                double os, double &fc, double &fw, double &fs) {
+                                                const long *__restrict__ srcOf, const HaloRec *__restrict__ rec, long q,
+                                                int fromX, double oc, double ow, double os, double &fc, double &fw,
+                                                double &fs) {
   auto inner = [&](int ii, int jj) { return ii >= 1 && ii <= d.sNx && jj >= 1 && jj <= d.sNy; };
   int i, j;
   long r;   // where the new value is computed
   if constexpr (SHORT) {
-    mg_ij_of<true>(d, q, i, j);
-    r = q;
-    if (!inner(i, j)) {
-      const long sq = srcOf[q];
-      if (sq >= 0) { r = sq; mg_ij_of<true>(d, r, i, j); }
-    }
+    const HaloRec h = rec[q];
+    r = h.at2;
+    i = h.i;
+    j = h.j;
   } else {
     const long sq = srcOf[q];
     r = sq >= 0 ? sq : q;
-    mg_ij_of<false>(d, r, i, j);
+    mg_ij_of(d, r, i, j);
   }
   // eta at qq = (ii, jj)
   auto eta = [&](long qq, int ii, int jj) {
     if constexpr (SHORT) {   // eta_exch's cases with (ii, jj) known: no index arithmetic
       if (inner(ii, jj)) return f.cg2d_b[qq];
-      const long sqq = srcOf[qq];
-      if (sqq >= 0) return f.cg2d_b[sqq];
+      const long sqq = rec[qq].at2;   // (a mapped point's source is another point)
+      if (sqq != qq) return f.cg2d_b[sqq];
       return fromX ? f.recip_Bo[qq] * f.cg2d_x[qq] : f.etaN[qq];
     } else {
       return FUSE ? eta_exch(d, f, srcOf, qq, fromX) : f.etaH[qq];
@@ -85,7 +71,7 @@ __device__ __forceinline__ void calc_r_star_fac(const Dims &d, const Params &p, 
     // reference's ranges, their halos then refilled through the vector map (calc_r_star())
     const long rv = (!SHORT && p.cubeCorners) ? q : r;
     int iv = i, jv = j;
-    if constexpr (!SHORT) mg_ij_of<false>(d, rv, iv, jv);
+    if constexpr (!SHORT) mg_ij_of(d, rv, iv, jv);
     if (iv >= 1 && iv <= d.sNx + 1 && jv >= 1 && jv <= d.sNy) {
       if (f.maskInW[rv] != 0.0) {
         const double tmp = f.rSurfW[rv] - f.rLowW[rv];
@@ -113,9 +99,14 @@ __device__ __forceinline__ void calc_r_star_fac(const Dims &d, const Params &p, 
 // empNext (MG_FUSE_PIPE, with FUSE): the next step's DO_OCEANIC_PHYS ran earlier in this step
 // and left its EmPmR in EmPmRnext (phys.h); this pass, the step's last reader of EmPmR, moves
 // it over once it has formed PmEpR -- each thread its own point.
-template <bool FUSE>
+// TAB (k_rstar_exch_phi's grid: FUSE, EXCH1, every tile): the same pass reading the topology from
+// the HaloRec table -- eta_exch's three cases from the record's flags, the factors by
+// calc_r_star_fac's SHORT form -- instead of dividing 64-bit offsets
+template <bool FUSE, bool TAB = false>
 __device__ __forceinline__ void calc_r_star_body(const Dims &d, const Params &p, const Fields &f,
-                                                 const long *__restrict__ srcOf, int lb, int fromX, int empNext = 0) {
+                                                 const long *__restrict__ srcOf, int lb, int fromX, int empNext = 0,
+                                                 const HaloRec *__restrict__ rec = nullptr) {
+  static_assert(FUSE || !TAB, "the table form is the fused pass's");
   const long q = (long)lb * blockDim.x + threadIdx.x;
   if (q >= d.n2 * d.nTiles) return;
   const int t = (int)(q / d.n2);
@@ -123,14 +114,20 @@ __device__ __forceinline__ void calc_r_star_body(const Dims &d, const Params &p,
   if constexpr (FUSE) {   // k_exch_etaH (kernels_solve.hip), atInit = 0
     if (p.nonlinFreeSurf > 0 && p.useRealFreshWaterFlux) f.PmEpR[q] = -f.EmPmR[q];
     if (empNext) f.EmPmR[q] = f.EmPmRnext[q];
-    const double x = eta_exch(d, f, srcOf, q, fromX);
+    double x;
+    if constexpr (TAB) {
+      const HaloRec h = rec[q];
+      x = (h.flags & (MG_HR_INTERIOR | MG_HR_MAPPED)) ? f.cg2d_b[h.at2] : fromX ? f.recip_Bo[q] * f.cg2d_x[q] : f.etaN[q];
+    } else {
+      x = eta_exch(d, f, srcOf, q, fromX);
+    }
     f.etaHnm1[q] = f.etaH[q];
     f.etaN[q] = x;
     f.etaH[q] = x;
   }
   const double oc = f.rStarFacC[q], ow = f.rStarFacW[q], os = f.rStarFacS[q];
   double fc, fw, fs;
-  calc_r_star_fac<FUSE>(d, p, f, srcOf, q, fromX, oc, ow, os, fc, fw, fs);
+  calc_r_star_fac<FUSE, true, TAB>(d, p, f, srcOf, rec, q, fromX, oc, ow, os, fc, fw, fs);
   f.rStarFacC[q] = fc;
   f.rStarFacW[q] = fw;
   f.rStarFacS[q] = fs;
@@ -148,11 +145,11 @@ __device__ __forceinline__ void calc_r_star_body(const Dims &d, const Params &p,
 // block of this grid writes) -- the same expressions on the same operands, so the same bits.
 template <bool WS>
 __device__ __forceinline__ void r_star_next_point(const Dims &d, const Params &p, const Fields &f,
-                                                  const long *__restrict__ srcOf, long q, int fromX, double &facC,
+                                                  const HaloRec *__restrict__ rec, long q, int fromX, double &facC,
                                                   double &dhC, double &dhW, double &dhS) {
   const double oc = f.rStarFacCPrev[q], ow = WS ? f.rStarFacWPrev[q] : 0.0, os = WS ? f.rStarFacSPrev[q] : 0.0;
   double fc, fw, fs;
-  calc_r_star_fac<true, WS, true>(d, p, f, srcOf, q, fromX, oc, ow, os, fc, fw, fs);
+  calc_r_star_fac<true, WS, true>(d, p, f, nullptr, rec, q, fromX, oc, ow, os, fc, fw, fs);
   facC = fc;
   dhC = (fc - oc) / p.deltaTFreeSurf;
   if constexpr (WS) {
@@ -165,11 +162,10 @@ __device__ __forceinline__ void r_star_next_point(const Dims &d, const Params &p
 // grid: at the exchange source of (i,j,t) where it has one (the value the exchange copies into
 // the point), else at the point itself (interior: stable; neither interior nor mapped: written by
 // nobody).  A source is never itself an image, so nothing in the grid writes where this reads.
-__device__ __forceinline__ long mg_at_source3(const Dims &d, const long *__restrict__ srcOf, int i, int j, int k, int t) {
-  if (i >= 1 && i <= d.sNx && j >= 1 && j <= d.sNy) return MG_I3(d, i, j, k, t);
-  const long sq = srcOf[MG_I2(d, i, j, t)];
-  if (sq < 0) return MG_I3(d, i, j, k, t);
-  return (sq / d.n2) * d.n3 + (long)(k - 1) * d.n2 + sq % d.n2;
+// The level-1 offset comes from the point's HaloRec (base3); level k lies (k-1)*n2 further.
+__device__ __forceinline__ long mg_at_source3(const Dims &d, const HaloRec *__restrict__ rec, int i, int j, int t) {
+  if (i >= 1 && i <= d.sNx && j >= 1 && j <= d.sNy) return MG_I3(d, i, j, 1, t);
+  return rec[MG_I2(d, i, j, t)].base3;
 }
 
 }  // namespace mgcm

@@ -291,11 +291,14 @@ class Model:
         'phi_pipelined': it also ran the next step's CALC_PHI_HYD and del2uv in each step's last
         grid (bit 32768, with 'pipelined').  'specialised': the fold's momentum and tracer
         right-hand-side grid ran the bodies compiled for global_ocean.90x40x15's option set
-        (bit 65536; only where the model's options are that set)."""
+        (bit 65536; only where the model's options are that set).  'solve_side_specialised': so
+        did, in the pipelined call, the grids on either side of the pressure solve -- the r* column
+        pass and the correction step with their riders (bit 131072, with 'specialised' and
+        'phi_pipelined')."""
         b = int(lib().mgcm_get_param(self.h, b"stepLayout"))
         return {"dyn_thermo_fused": bool(b & 1), "thermo_second_stream": bool(b & 4),
                 "late_join": bool(b & 8), "pipelined": bool(b & 16), "phi_pipelined": bool(b & 32),
-                "specialised": bool(b & 64)}
+                "specialised": bool(b & 64), "solve_side_specialised": bool(b & 128)}
 
     def ptracers_route(self):
         """How the last PTRACERS_INTEGRATE issued was launched (mgcm_get_param 'ptrRoute',
