@@ -83,19 +83,20 @@ def advect_xy_ab3_c4(nSx=1, nSy=2):
     return g, params, state
 
 
-def baroclinic_gyre(nSx=2, nSy=2, data_dir=None, tempAdvScheme=2):
+def baroclinic_gyre(nSx=2, nSy=2, data_dir=None, tempAdvScheme=2, OL=2):
     """verification/tutorial_baroclinic_gyre: 62x62x15 on a 1-degree spherical-polar
     grid, code/SIZE.h sNx=sNy=31, OL=2, nSx=nSy=2; input/data: viscAh=5000,
     viscAr=1e-2, no_slip_bottom=F, diffKhT=1000, diffKrT=1e-5, ivdc_kappa=1,
     implicitDiffusion, LINEAR EOS tAlpha=2e-4 sBeta=0, rhoNil=999.8, exactConserv,
     saltStepping=F, deltaT=1200, tauThetaClimRelax=2592000 (SST_relax.bin),
     xgOrigin=-1, ygOrigin=14, delR as below.  Resolved parameters are pinned
-    against the output.txt dump (tests/test_oracle_3d.py)."""
+    against the output.txt dump (tests/test_oracle_3d.py).  OL: another overlap than SIZE.h's
+    (OS7MP, tempAdvScheme=7, needs 4)."""
     d = data_dir or os.path.join(GOLDEN, "tutorial_baroclinic_gyre")
     Nx = Ny = 62
     Nr = 15
     sNx, sNy = Nx // nSx, Ny // nSy
-    g = Grid(sNx, sNy, 2, 2, Nr, nSx, nSy)
+    g = Grid(sNx, sNy, OL, OL, Nr, nSx, nSy)
     g.ini_vertical_grid(BAROCLINIC_DELR)
     g.ini_spherical_polar_grid(np.full(Nx, 1.0), np.full(Ny, 1.0), -1.0, 14.0)
     g.ini_cori(selectCoriMap=2)
@@ -126,15 +127,16 @@ def baroclinic_gyre(nSx=2, nSy=2, data_dir=None, tempAdvScheme=2):
     return g, params, state
 
 
-def advect_xy(nSx=1, nSy=2):
+def advect_xy(nSx=1, nSy=2, OL=3):
     """verification/advect_xy: 20x20x1 doubly-periodic cartesian box (10 km cells,
     code/SIZE.h sNx=20, sNy=10, OL=3, nSy=2), momStepping=F, uniform u = v = 1 m/s
     (code/ini_vel.F), a salt disc of +1 psu (code/ini_salt.F), saltAdvScheme=33
     (DST3 flux-limited, multi-dimensional), deltaT=2500.  Only salt is stepped here
-    (theta uses scheme 80 in the reference and does not feed back)."""
+    (theta uses scheme 80 in the reference and does not feed back).  OL: another overlap than
+    SIZE.h's (OS7MP, saltAdvScheme=7, needs 4)."""
     Nx = Ny = 20
     sNx, sNy = Nx // nSx, Ny // nSy
-    g = Grid(sNx, sNy, 3, 3, 1, nSx, nSy)
+    g = Grid(sNx, sNy, OL, OL, 1, nSx, nSy)
     g.ini_vertical_grid([10.0e3])
     g.ini_cartesian_grid(np.full(Nx, 10.0e3), np.full(Ny, 10.0e3), 0.0, 0.0)
     g.ini_cori(0.0, 0.0, selectCoriMap=1)

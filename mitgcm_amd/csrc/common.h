@@ -444,6 +444,21 @@ __device__ __forceinline__ void sfp_rhs_column(const Dims &d, const Params &p, c
   f.cg2d_b[q] = b;
 }
 
+// The flux-function families of the multi-dimensional (direct-space-time) advection, a template
+// parameter of GAD_ADVECTION's pass kernels (kernels_thermo.hip adv_flux_h / adv_flux_r): the
+// scheme is compiled in, so OS7MP's long body costs the DST3 kernels no register.
+//   MG_ADV_DST3    30 (DST3) and 33 (DST3FL)       reach 2 cells
+//   MG_ADV_DST2U1   1 (upwind) and 20 (DST2)        reach 1 cell
+//   MG_ADV_OS7MP    7 (OS7MP)                       reach 4 cells
+enum { MG_ADV_DST3 = 0, MG_ADV_DST2U1 = 1, MG_ADV_OS7MP = 2, MG_ADV_NFAM = 3 };
+// run `stmt` with FAM the compile-time constant of the run-time family `fam`
+#define MG_ADV_FAMILY(fam, stmt)                                                   \
+  do {                                                                             \
+    if ((fam) == MG_ADV_DST2U1) { constexpr int FAM = MG_ADV_DST2U1; stmt; }       \
+    else if ((fam) == MG_ADV_OS7MP) { constexpr int FAM = MG_ADV_OS7MP; stmt; }    \
+    else { constexpr int FAM = MG_ADV_DST3; stmt; }                                \
+  } while (0)
+
 // One tracer of TEMP_INTEGRATE / SALT_INTEGRATE (temp_integrate.F, salt_integrate.F).
 struct TracerArgs {
   const double *tr;     // tracer at the start of the step (halo-exchanged)
@@ -455,8 +470,9 @@ struct TracerArgs {
   const double *sfc;    // surface forcing (surfaceForcingT/S), or null
   double diffKh, diffKr, dT;
   int advection, multiDim, useAB, forcing;
-  int limiter;          // multi-dim face fluxes: 1 DST3FL (scheme 33), 0 DST3 (scheme 30)
-  int scheme;           // the advection scheme (2 C2, 3 U3, 4 C4 inside GAD_CALC_RHS; 30/33 multi-dim)
+  int advFamily;        // multi-dim face fluxes: the scheme family the pass kernels are compiled for (MG_ADV_*)
+  int advParm;          // and its parameter: DST3 1 = the flux limiter (33; 0 = 30), DST2U1 1 = DST2 (20; 0 = upwind, 1)
+  int scheme;           // the advection scheme (2 C2, 3 U3, 4 C4 inside GAD_CALC_RHS; 30/33, 1/20, 7 multi-dim)
   double *gNm2;         // ADAMS_BASHFORTH3: gtNm(:,:,:,2) (gNm1 is slot 1)
   // passive tracers' forcing (pkg/ptracers; "off" for theta and salt, whose arithmetic it leaves alone)
   double relaxRate;     // 1/surfRelaxTau, 0: no surface relaxation (ptracers_forcing_surf.F)

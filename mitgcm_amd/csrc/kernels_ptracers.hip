@@ -13,7 +13,9 @@
 // device table and run the bodies the one-tracer kernels run (adv_x/y/r_body, the advg_*_point
 // functions, tracer_rhs_body, tracer_impl_body: kernels_thermo.hip) -- the same bits, at most
 // five launches whatever the number of tracers (six on a lat-lon grid when some take GM/Redi
-// and some do not).  The general form -- EXCH2 topologies (cubeCorners) and
+// and some do not) while the multi-dimensional tracers are of one scheme family; each further
+// family present (common.h MG_ADV_*: {30, 33}, {1, 20}, {7}) adds its own pass launches, 3 on
+// the lat-lon two-pass route and 2 in the general form (launch_ptracers_batch).  The general form -- EXCH2 topologies (cubeCorners) and
 // GAD_MULTIDIM_COMPRESSIBLE -- runs every pass of a (tracer, tile, level) in one workgroup
 // with the level's frame in LDS (k_ptr_advg_plane).  Opt-in, MGCM_PTR_BATCH=1; where it wins
 // and where the tracers hide beside the pressure solve either way: model.hip ptr_batched,
@@ -37,32 +39,35 @@ __device__ __forceinline__ PtrBlock ptr_block(int nbPer) {
   return PtrBlock{lbAll / nbPer, lbAll % nbPer};
 }
 
-// GAD_ADVECTION's X, Y and vertical passes of the multi-dimensional tracers in `list`
+// GAD_ADVECTION's X, Y and vertical passes of the multi-dimensional tracers in `list`, all of
+// the scheme family FAM (common.h MG_ADV_*: the flux function is compiled in)
+template <int FAM>
 __global__ void __launch_bounds__(256) k_ptr_adv_x(Dims d, Fields f, const TracerArgs *__restrict__ tab,
                                                    const int *__restrict__ list, int nList, int nbPer) {
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
-  adv_x_body(d, f, a, b.lb);
+  adv_x_body<FAM>(d, f, a, b.lb);
 }
+template <int FAM>
 __global__ void __launch_bounds__(256) k_ptr_adv_y(Dims d, Fields f, const TracerArgs *__restrict__ tab,
                                                    const int *__restrict__ list, int nList, int nbPer) {
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
-  adv_y_body(d, f, a, b.lb);
+  adv_y_body<FAM>(d, f, a, b.lb);
 }
 // COMP: GAD_MULTIDIM_COMPRESSIBLE (the local volume in adv2); gen: the general form's loc is
 // adv1 (k_ptr_advg_plane), the lat-lon passes' is adv2 (k_ptr_adv_y) -- launch_tracer_step's
 // three k_adv_r launches
-template <bool COMP>
+template <bool COMP, int FAM>
 __global__ void __launch_bounds__(256) k_ptr_adv_r(Dims d, Params p, Fields f, const TracerArgs *__restrict__ tab,
                                                    const int *__restrict__ list, int nList, int nbPer, int gen) {
   const PtrBlock b = ptr_block(nbPer);
   if (b.it >= nList) return;
   const TracerArgs a = tab[list[b.it]];
   const double *L = gen ? a.adv1 : a.adv2;
-  adv_r_body<COMP>(d, p, f, a, L, COMP ? a.adv2 : L, b.lb);
+  adv_r_body<COMP, FAM>(d, p, f, a, L, COMP ? a.adv2 : L, b.lb);
 }
 
 // GAD_ADVECTION's general form (cube tiles and / or GAD_MULTIDIM_COMPRESSIBLE: the explicit
@@ -76,6 +81,7 @@ __global__ void __launch_bounds__(256) k_ptr_adv_r(Dims d, Params p, Fields f, c
 // past the frame skip the work, never a barrier.  Nothing here touches gTscr, which the
 // tracers of a batch would share; the interior of loc (vol) goes to the tracer's own adv1
 // (adv2), all that adv_r_body reads.
+template <int FAM>
 __global__ void __launch_bounds__(1024) k_ptr_advg_plane(Dims d, Fields f, const TracerArgs *__restrict__ tab,
                                                         const int *__restrict__ list, int nList, int cube, int comp) {
   extern __shared__ double ptrFrame[];
@@ -105,7 +111,7 @@ __global__ void __launch_bounds__(1024) k_ptr_advg_plane(Dims d, Fields f, const
       for (int r = 0; r < trips; r++) {
         const int q = r * nth + tid;
         if (q < np)
-          advg_flux_point(d, f, a, ipass, ydir, cube != 0, face, edges, 1 - d.OLx + q % nx, 1 - d.OLy + q / nx, k, t, L, G);
+          advg_flux_point<FAM>(d, f, a, ipass, ydir, cube != 0, face, edges, 1 - d.OLx + q % nx, 1 - d.OLy + q / nx, k, t, L, G);
       }
       __syncthreads();
       if (cube) {
@@ -186,29 +192,42 @@ bool ptr_batch_ok(const Dims &d, const Params &p, bool md) {
 }
 
 // tab: the TracerArgs of every tracer (device); lists: [md | all], the multi-dimensional
-// tracers and every tracer in launch order (device), nMd and nAll entries, the second list
-// starting at lists + stride, its first nGM tracers the ones that take GM/Redi.  nLaunch (or
-// null): the kernel launches issued are added to it.  (The lists are all the kernels know of
-// who they step: theta and salt could join one with TracerArgs of their own.)
+// tracers and every tracer in launch order (device), the second list starting at lists + stride,
+// its first nGM tracers the ones that take GM/Redi.  The multi-dimensional list is sorted by
+// scheme family, nMdFam[MG_ADV_NFAM] tracers each: the passes of a family are launches of their
+// own (the flux function is a template parameter), as the right-hand side's GM / non-GM kinds are.
+// nLaunch (or null): the kernel launches issued are added to it -- per family present 3 on the
+// lat-lon two-pass route and 2 in the general form, then 1 or 2 right-hand sides and the
+// implicit solve.  (The lists are all the kernels know of who they step: theta and salt could
+// join one with TracerArgs of their own.)
 hipError_t launch_ptracers_batch(const Dims &d, const Params &p, const Fields &f, const TracerArgs *tab, const int *lists,
-                                 int stride, int nMd, int nAll, int nGM, const int *iterPtr, hipStream_t s, int *nLaunch) {
+                                 int stride, const int *nMdFam, int nAll, int nGM, const int *iterPtr, hipStream_t s,
+                                 int *nLaunch) {
   if (nAll <= 0) return hipSuccess;
   int nl = 0;
   const dim3 blk(MG_PLANE_THREADS);
   const int nbI = (int)mg_plane_blocks(d.sNx, d.sNy, d.nT * d.Nr), nbF = (int)mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr);
-  if (nMd > 0) {
+  const int *md = lists;
+  for (int fam = 0; fam < MG_ADV_NFAM; md += nMdFam[fam], fam++) {
+    const int nMd = nMdFam[fam];
+    if (nMd <= 0) continue;
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: the per-point X and Y passes
-      hipLaunchKernelGGL(k_ptr_adv_x, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbF);
-      hipLaunchKernelGGL(k_ptr_adv_y, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, f, tab, lists, nMd, nbI);
-      hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 0);
+      MG_ADV_FAMILY(fam, hipLaunchKernelGGL(k_ptr_adv_x<FAM>, dim3((unsigned)(nbF * nMd)), blk, 0, s, d, f, tab, md, nMd, nbF));
+      MG_ADV_FAMILY(fam, hipLaunchKernelGGL(k_ptr_adv_y<FAM>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, f, tab, md, nMd, nbI));
+      MG_ADV_FAMILY(fam, hipLaunchKernelGGL((k_ptr_adv_r<false, FAM>), dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, md,
+                                            nMd, nbI, 0));
       nl += 3;
     } else {                // the general form: every pass of a level in one workgroup
       if (ptr_plane_lds(d, p) > MG_PTR_PLANE_LDS_MAX) return hipErrorInvalidValue;   // (ptr_batch_ok was not asked)
-      hipLaunchKernelGGL(k_ptr_advg_plane, dim3((unsigned)(d.nT * d.Nr * nMd)), dim3(ptr_plane_threads(d)), ptr_plane_lds(d, p), s,
-                         d, f, tab, lists, nMd, (int)cube, (int)comp);
-      if (comp) hipLaunchKernelGGL(k_ptr_adv_r<true>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
-      else hipLaunchKernelGGL(k_ptr_adv_r<false>, dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, lists, nMd, nbI, 1);
+      MG_ADV_FAMILY(fam, hipLaunchKernelGGL(k_ptr_advg_plane<FAM>, dim3((unsigned)(d.nT * d.Nr * nMd)), dim3(ptr_plane_threads(d)),
+                                            ptr_plane_lds(d, p), s, d, f, tab, md, nMd, (int)cube, (int)comp));
+      if (comp)
+        MG_ADV_FAMILY(fam, hipLaunchKernelGGL((k_ptr_adv_r<true, FAM>), dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, md,
+                                              nMd, nbI, 1));
+      else
+        MG_ADV_FAMILY(fam, hipLaunchKernelGGL((k_ptr_adv_r<false, FAM>), dim3((unsigned)(nbI * nMd)), blk, 0, s, d, p, f, tab, md,
+                                              nMd, nbI, 1));
       nl += 2;
     }
   }

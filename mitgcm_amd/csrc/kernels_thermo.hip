@@ -6,9 +6,11 @@
 //                   IVDConvCount from GRAD_SIGMA/CALC_IVDC (grad_sigma.F:103-117, calc_ivdc.F:60-71).
 //   tracer step     TEMP_INTEGRATE / SALT_INTEGRATE (model/src/temp_integrate.F) for one
 //                   tracer: GAD C2 advection (gad_c2_adv_x/y/r.F) with AB2 on the tendency
-//                   (adams_bashforth2.F:81-88), or the multi-dimensional DST3 flux-limited
-//                   advection (gad_advection.F + gad_dst3fl_adv_x/y/r.F, k_adv_x/y/r) stepped
-//                   forward; Laplacian diffusion (gad_diff_x/y.F), surface forcing
+//                   (adams_bashforth2.F:81-88), or the multi-dimensional advection of
+//                   gad_advection.F (k_adv_x/y/r, k_advg_*) stepped forward, with the flux
+//                   function of a direct-space-time scheme compiled in: DST3 / DST3FL
+//                   (gad_dst3_adv_*.F, gad_dst3fl_adv_*.F), upwind / DST2 (gad_dst2u1_adv_*.F)
+//                   or OS7MP (gad_os7mp_adv_*.F); Laplacian diffusion (gad_diff_x/y.F), surface forcing
 //                   (apply_forcing.F:687-695), TIMESTEP_TRACER, vertical diffusion explicit
 //                   (gad_diff_r.F) or implicit (GAD_IMPLICIT_R, gad_implicit_r.F:96-140, Thomas
 //                   sweep of SOLVE_TRIDIAGONAL), CYCLE_TRACER.
@@ -139,11 +141,166 @@ __device__ __forceinline__ double dst3fl_h(double uTr, double cfl, double tm2, d
   return 0.5 * (uTr + fabs(uTr)) * (tm1 + psiP * Rj) + 0.5 * (uTr - fabs(uTr)) * (t0 - psiM * Rj);
 }
 
+// GAD_DST2U1_ADV_X/Y (gad_dst2u1_adv_x.F:57-81, _y.F): first-order upwind (scheme 1, xLimit = 0)
+// and DST2 (scheme 20, xLimit = 1) in the robust uAbs form; tm1 is the cell west / south of the face
+__device__ __forceinline__ double dst2u1_h(double uTr, double cfl, double tm1, double t0, double xLimit) {
+  const double uAbs = fabs(uTr) * (1.0 - xLimit * (1.0 - cfl));
+  return (uTr + uAbs) * 0.5 * tm1 + (uTr - uAbs) * 0.5 * t0;
+}
+// GAD_DST2U1_ADV_R (gad_dst2u1_adv_r.F:57-90): tkm1 above the face, tk below; mkm1 = maskC(km1)
+__device__ __forceinline__ double dst2u1_r(double rTr, double cfl, double tkm1, double tk, double mkm1, double rkSign,
+                                           double rLimit) {
+  const double wAbs = fabs(rTr) * rkSign * (1.0 - rLimit * (1.0 - cfl));
+  return mkm1 * ((rTr + wAbs) * 0.5 * tkm1 + (rTr - wAbs) * 0.5 * tk);
+}
+
+// GAD_OS7MP_ADV_X/Y/R (gad_os7mp_adv_x.F:113-205, _y.F, _r.F:109-201) from the upstream-ordered
+// stencil: Qi the upstream cell of the face, Qip the downstream one; Msk* the mask products'
+// factors in the same order.  The six corrections, the recip_DelIp / recip_DelI forms and the MP
+// limiter in the reference's operation order.  tr = 0 (:206-207) is the caller's select.
+struct Os7Stencil { double Qippp, Qipp, Qip, Qi, Qim, Qimm, Qimmm, MskIpp, MskIp, MskI, MskIm, MskImm, MskImmm; };
+__device__ __forceinline__ double os7mp_core(double tr, double cfl, const Os7Stencil &s) {
+  const double Eps = 1.0e-20;
+  double Fac = 1.0;
+  const double DelP = (s.Qip - s.Qi) * s.MskI;
+  double Phi = Fac * DelP;
+  Fac = Fac * (cfl + 1.0) / 3.0;
+  const double DelM = (s.Qi - s.Qim) * s.MskIm;
+  const double Del2 = DelP - DelM;
+  Phi = Phi - Fac * Del2;
+  Fac = Fac * (cfl - 2.0) / 4.0;
+  const double DelPP = (s.Qipp - s.Qip) * s.MskIp * s.MskI;
+  const double Del2P = DelPP - DelP;
+  const double Del3P = Del2P - Del2;
+  Phi = Phi + Fac * Del3P;
+  Fac = Fac * (cfl - 3.0) / 5.0;
+  const double DelMM = (s.Qim - s.Qimm) * s.MskImm * s.MskIm;
+  const double Del2M = DelM - DelMM;
+  const double Del3M = Del2 - Del2M;
+  const double Del4 = Del3P - Del3M;
+  Phi = Phi + Fac * Del4;
+  Fac = Fac * (cfl + 2.0) / 6.0;
+  const double DelPPP = (s.Qippp - s.Qipp) * s.MskIpp * s.MskIp * s.MskI;
+  (void)DelPPP;   // (gad_os7mp_adv_x.F:138-139: Del2PP is formed from DelPP and DelP, DelPPP is not used)
+  const double Del2PP = DelPP - DelP;
+  const double Del3PP = Del2PP - Del2P;
+  const double Del4P = Del3PP - Del3P;
+  const double Del5P = Del4P - Del4;
+  Phi = Phi + Fac * Del5P;
+  Fac = Fac * (cfl + 2.0) / 7.0;
+  const double DelMMM = (s.Qimm - s.Qimmm) * s.MskImmm * s.MskImm * s.MskIm;
+  const double Del2MM = DelMM - DelMMM;
+  const double Del3MM = Del2M - Del2MM;
+  const double Del4M = Del3M - Del3MM;
+  const double Del5M = Del4 - Del4M;
+  const double Del6 = Del5P - Del5M;
+  Phi = Phi - Fac * Del6;
+
+  const double DelIp = (s.Qip - s.Qi) * s.MskI;
+  const double recip_DelIp = copysign(1.0, DelIp) / fmax(fabs(DelIp), Eps);
+  Phi = Phi * recip_DelIp;
+  const double DelI = (s.Qi - s.Qim) * s.MskIm;
+  const double recip_DelI = copysign(1.0, DelI) / fmax(fabs(DelI), Eps);
+  const double rp1h = DelI * recip_DelIp;
+  const double rp1h_cfl = rp1h / (cfl + Eps);
+  // MP limiter
+  const double d2 = Del2, d2p1 = Del2P, d2m1 = Del2M;
+  double A = 4.0 * d2 - d2p1, B = 4.0 * d2p1 - d2, C = d2, D = d2p1;
+  const double dp1h = fmax(fmin(fmin(A, B), fmin(C, D)), 0.0) + fmin(fmax(fmax(A, B), fmax(C, D)), 0.0);
+  A = 4.0 * d2m1 - d2; B = 4.0 * d2 - d2m1; C = d2m1; D = d2;
+  const double dm1h = fmax(fmin(fmin(A, B), fmin(C, D)), 0.0) + fmin(fmax(fmax(A, B), fmax(C, D)), 0.0);
+  const double PhiMD = 1.0 / (1.0 - cfl) * (DelIp - dp1h) * recip_DelIp;
+  const double PhiLC = rp1h_cfl * (1.0 + dm1h * recip_DelI);
+  const double PhiMin = fmax(fmin(0.0, PhiMD), fmin(fmin(0.0, 2.0 * rp1h_cfl), PhiLC));
+  const double PhiMax = fmin(fmax(2.0 / (1.0 - cfl), PhiMD), fmax(fmax(0.0, 2.0 * rp1h_cfl), PhiLC));
+  Phi = fmax(PhiMin, fmin(Phi, PhiMax));
+  const double Psi = Phi * 0.5 * (1.0 - cfl);
+  return tr * (s.Qi + Psi * DelIp);
+}
+// horizontal face between cells -1 and 0: Q(o), M(o) the tracer and the face mask at offset o
+// from the face's own cell (gad_os7mp_adv_x.F:66-111); the upstream side by selects
+template <class QF, class MF>
+__device__ __forceinline__ double os7mp_h(double uTr, double cfl, QF Q, MF M) {
+  const double qm4 = Q(-4), qm3 = Q(-3), qm2 = Q(-2), qm1 = Q(-1), q0 = Q(0), qp1 = Q(1), qp2 = Q(2), qp3 = Q(3);
+  const double mm3 = M(-3), mm2 = M(-2), mm1 = M(-1), m0 = M(0), mp1 = M(1), mp2 = M(2), mp3 = M(3);
+  const bool pos = uTr > 0.0;
+  Os7Stencil s;
+  s.Qippp = pos ? qp2 : qm3; s.Qipp = pos ? qp1 : qm2; s.Qip = pos ? q0 : qm1; s.Qi = pos ? qm1 : q0;
+  s.Qim = pos ? qm2 : qp1; s.Qimm = pos ? qm3 : qp2; s.Qimmm = pos ? qm4 : qp3;
+  s.MskIpp = pos ? mp2 : mm2; s.MskIp = pos ? mp1 : mm1; s.MskI = m0;
+  s.MskIm = pos ? mm1 : mp1; s.MskImm = pos ? mm2 : mp2; s.MskImmm = pos ? mm3 : mp3;
+  const double uT = os7mp_core(uTr, cfl, s);
+  return uTr != 0.0 ? uT : 0.0;
+}
+// vertical face through the top of level k (gad_os7mp_adv_r.F:48-107): Q(kk), M(kk) the tracer and
+// maskC at level kk; the clipped indices km4..kp3 with the factors that zero a clipped difference
+template <class QF, class MF>
+__device__ __forceinline__ double os7mp_r(double rTr, double cfl, int k, int Nr, QF Q, MF M) {
+  const int km4 = k - 4 > 1 ? k - 4 : 1, km3 = k - 3 > 1 ? k - 3 : 1, km2 = k - 2 > 1 ? k - 2 : 1, km1 = k - 1 > 1 ? k - 1 : 1;
+  const int kp1 = k + 1 < Nr ? k + 1 : Nr, kp2 = k + 2 < Nr ? k + 2 : Nr, kp3 = k + 3 < Nr ? k + 3 : Nr;
+  const double qm4 = Q(km4), qm3 = Q(km3), qm2 = Q(km2), qm1 = Q(km1), q0 = Q(k), qp1 = Q(kp1), qp2 = Q(kp2), qp3 = Q(kp3);
+  const double fm3 = M(km3) * (double)(km3 - km4), fm2 = M(km2) * (double)(km2 - km3), fm1 = M(km1) * (double)(km1 - km2);
+  const double f0 = M(k) * (double)(k - km1);
+  const double fp1 = M(kp1) * (double)(kp1 - k), fp2 = M(kp2) * (double)(kp2 - kp1), fp3 = M(kp3) * (double)(kp3 - kp2);
+  const bool neg = rTr < 0.0;
+  Os7Stencil s;
+  s.Qippp = neg ? qp2 : qm3; s.Qipp = neg ? qp1 : qm2; s.Qip = neg ? q0 : qm1; s.Qi = neg ? qm1 : q0;
+  s.Qim = neg ? qm2 : qp1; s.Qimm = neg ? qm3 : qp2; s.Qimmm = neg ? qm4 : qp3;
+  s.MskIpp = neg ? fp2 : fm2; s.MskIp = neg ? fp1 : fm1; s.MskI = f0;
+  s.MskIm = neg ? fm1 : fp1; s.MskImm = neg ? fm2 : fp2; s.MskImmm = neg ? fm3 : fp3;
+  const double wT = os7mp_core(rTr, cfl, s);
+  return rTr != 0.0 ? wT : 0.0;
+}
+
+// The multi-dimensional face flux of a scheme family, compiled in (template parameter of the
+// pass bodies and their kernels; TracerArgs::advFamily picks the instantiation on the host):
+// MG_ADV_DST3 {30, 33; advParm 1: the flux limiter}, MG_ADV_DST2U1 {1, 20; advParm 1: DST2},
+// MG_ADV_OS7MP {7}.  Every horizontal call site -- adv_x_body, adv_y_body, advg_flux_point --
+// and adv_r_body go through MG_ADV_FLUX_H / MG_ADV_FLUX_R_RETURN, so the lat-lon passes and the
+// EXCH2 drivers run one statement of each flux.  They are macros over the call site's accessor
+// macros Q(o), M(o): the DST3 family then compiles to the registers it had before the
+// families (as functions over accessor lambdas k_adv_x / _y took 4 and 2 VGPRs more;
+// profiles/r17/adv_schemes/resource_usage.md).
+// AdvFaces: the faces the routine computes along the pass's direction of a tile with n points
+// and overlap OL, lo - OL .. n + OL + hi; the others are the zeros its own loop bounds leave
+// (gad_dst3fl_adv_x.F:66-72, gad_dst2u1_adv_x.F:60-64, gad_os7mp_adv_x.F:50-60).
+template <int FAM> struct AdvFaces {
+  static constexpr int lo = FAM == MG_ADV_OS7MP ? 5 : FAM == MG_ADV_DST2U1 ? 2 : 3;
+  static constexpr int hi = FAM == MG_ADV_OS7MP ? -3 : FAM == MG_ADV_DST2U1 ? 0 : -1;
+};
+#define MG_ADV_FLUX_H(FAM, uTr, cfl, parm, Q, M)                                                          \
+  (FAM == MG_ADV_DST2U1 ? dst2u1_h(uTr, cfl, Q(-1), Q(0), (parm) ? 1.0 : 0.0)                              \
+   : FAM == MG_ADV_OS7MP ? os7mp_h(uTr, cfl, [&](int o_) { return Q(o_); }, [&](int o_) { return M(o_); }) \
+                         : dst3fl_h(uTr, cfl, Q(-2), Q(-1), Q(0), Q(1), M(-1), M(0), M(1), parm))
+// the vertical face through the top of level kk, 1 < kk <= Nr, as the value a lambda returns:
+// Q(k2), M(k2) the tracer and maskC of level k2, rT and cfl expressions of kk.  The DST3 family is
+// GAD_DST3FL_ADV_R (gad_dst3fl_adv_r.F:70-119; parm = 0: GAD_DST3_ADV_R, gad_dst3_adv_r.F:70-119).
+// Statements with their own returns: it must be the last thing in a lambda that returns double
+// (adv_r_body's fver), and it declares km2, km1, kp1, Rjp, Rj, Rjm, cfl, d0, d1, rT, psiP, psiM there.
+#define MG_ADV_FLUX_R_RETURN(FAM, rT_, cfl_, kk, Nr, parm, rkSign, Q, M)                                             \
+  if (FAM == MG_ADV_DST2U1) return dst2u1_r(rT_, cfl_, Q(kk - 1), Q(kk), M(kk - 1), rkSign, (parm) ? 1.0 : 0.0);      \
+  if (FAM == MG_ADV_OS7MP)                                                                                           \
+    return os7mp_r(rT_, cfl_, kk, Nr, [&](int k_) { return Q(k_); }, [&](int k_) { return M(k_); });                 \
+  const int km2 = kk - 2 > 1 ? kk - 2 : 1, km1 = kk - 1 > 1 ? kk - 1 : 1, kp1 = kk + 1 < Nr ? kk + 1 : Nr;           \
+  const double Rjp = (Q(kk) - Q(kp1)) * M(kp1);                                                                      \
+  const double Rj = (Q(km1) - Q(kk)) * M(kk) * M(km1);                                                               \
+  const double Rjm = (Q(km2) - Q(km1)) * M(km1);                                                                     \
+  const double cfl = cfl_;                                                                                           \
+  const double oneSixth = 1.0 / 6.0;                                                                                 \
+  const double d0 = (2.0 - cfl) * (1.0 - cfl) * oneSixth, d1 = (1.0 - cfl * cfl) * oneSixth;                         \
+  const double rT = rT_;                                                                                             \
+  if (!(parm))                                                                                                       \
+    return 0.5 * (rT + fabs(rT)) * (Q(kk) + (d0 * Rj + d1 * Rjp)) + 0.5 * (rT - fabs(rT)) * (Q(km1) - (d0 * Rj + d1 * Rjm)); \
+  const double psiP = dst3fl_limit(d0, d1, dst3fl_theta(Rj, Rjm), cfl);                                              \
+  const double psiM = dst3fl_limit(d0, d1, dst3fl_theta(Rj, Rjp), cfl);                                              \
+  return 0.5 * (rT + fabs(rT)) * (Q(kk) + psiM * Rj) + 0.5 * (rT - fabs(rT)) * (Q(km1) - psiP * Rj)
+
 // GAD_ADVECTION (gad_advection.F), lat-lon operator splitting (npass = 2), X pass:
 // loc1 = T - dT/(h drF rA) * (afx(i+1) - afx(i) - T*(uTrans(i+1) - uTrans(i))) * maskInC
 // on i = 2-OLx..sNx+OLx-1, every j; elsewhere loc1 = T.
 // (the three passes as device functions of a logical block id: k_adv_x/y/r run them for one
 // tracer, the batched passive-tracer kernels for several, kernels_ptracers.hip)
+template <int FAM>
 __device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const TracerArgs &a, int lb) {
   MG_PLANE_LB(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
@@ -154,12 +311,14 @@ __device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const
   if (i >= 2 - d.OLx && i <= d.sNx + d.OLx - 1) {
     const double drF = f.drF[k - 1], dT = a.dT;
     auto uTr = [&](int ii) { return a.advU[MG_I3(d, ii, j, k, t)] * (f.dyG[MG_I2(d, ii, j, t)] * drF * f.hFacW[MG_I3(d, ii, j, k, t)]); };
-    auto afx = [&](int ii) {   // zero at i = 1-OLx, 2-OLx, sNx+OLx
-      if (ii < 3 - d.OLx || ii > d.sNx + d.OLx - 1) return 0.0;
+    auto afx = [&](int ii) {   // zero outside the scheme's own faces (DST3: at i = 1-OLx, 2-OLx, sNx+OLx)
+      if (ii < AdvFaces<FAM>::lo - d.OLx || ii > d.sNx + d.OLx + AdvFaces<FAM>::hi) return 0.0;
       const double cfl = fabs(a.advU[MG_I3(d, ii, j, k, t)] * dT * f.recip_dxC[MG_I2(d, ii, j, t)]);
-      return dst3fl_h(uTr(ii), cfl, T[MG_I3(d, ii - 2, j, k, t)], T[MG_I3(d, ii - 1, j, k, t)], T[MG_I3(d, ii, j, k, t)],
-                      T[MG_I3(d, ii + 1, j, k, t)], f.maskW[MG_I3(d, ii - 1, j, k, t)], f.maskW[MG_I3(d, ii, j, k, t)],
-                      f.maskW[MG_I3(d, ii + 1, j, k, t)], a.limiter);
+#define QX(o) T[MG_I3(d, ii + (o), j, k, t)]
+#define MX(o) f.maskW[MG_I3(d, ii + (o), j, k, t)]
+      return MG_ADV_FLUX_H(FAM, uTr(ii), cfl, a.advParm, QX, MX);
+#undef QX
+#undef MX
     };
     const long q = MG_I2(d, i, j, t);
     v = v - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
@@ -167,10 +326,12 @@ __device__ __forceinline__ void adv_x_body(const Dims &d, const Fields &f, const
   }
   a.adv1[q3] = v;
 }
-__global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) { adv_x_body(d, f, a, mg_xcd_block()); }
+template <int FAM>
+__global__ void __launch_bounds__(256) k_adv_x(Dims d, Fields f, TracerArgs a) { adv_x_body<FAM>(d, f, a, mg_xcd_block()); }
 
 // Y pass on the interior (the only rows the vertical pass and the tendency use):
 // loc2 = loc1 - dT/(h drF rA) * (afy(j+1) - afy(j) - T*(vTrans(j+1) - vTrans(j))) * maskInC
+template <int FAM>
 __device__ __forceinline__ void adv_y_body(const Dims &d, const Fields &f, const TracerArgs &a, int lb) {
   MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
@@ -179,23 +340,26 @@ __device__ __forceinline__ void adv_y_body(const Dims &d, const Fields &f, const
   const long q3 = MG_I3(d, i, j, k, t);
   const double drF = f.drF[k - 1], dT = a.dT;
   auto vTr = [&](int jj) { return a.advV[MG_I3(d, i, jj, k, t)] * (f.dxG[MG_I2(d, i, jj, t)] * drF * f.hFacS[MG_I3(d, i, jj, k, t)]); };
-  auto afy = [&](int jj) {   // zero at j = 1-OLy, 2-OLy, sNy+OLy
-    if (jj < 3 - d.OLy || jj > d.sNy + d.OLy - 1) return 0.0;
+  auto afy = [&](int jj) {   // zero outside the scheme's own faces (DST3: at j = 1-OLy, 2-OLy, sNy+OLy)
+    if (jj < AdvFaces<FAM>::lo - d.OLy || jj > d.sNy + d.OLy + AdvFaces<FAM>::hi) return 0.0;
     const double cfl = fabs(a.advV[MG_I3(d, i, jj, k, t)] * dT * f.recip_dyC[MG_I2(d, i, jj, t)]);
-    return dst3fl_h(vTr(jj), cfl, L1[MG_I3(d, i, jj - 2, k, t)], L1[MG_I3(d, i, jj - 1, k, t)], L1[MG_I3(d, i, jj, k, t)],
-                    L1[MG_I3(d, i, jj + 1, k, t)], f.maskS[MG_I3(d, i, jj - 1, k, t)], f.maskS[MG_I3(d, i, jj, k, t)],
-                    f.maskS[MG_I3(d, i, jj + 1, k, t)], a.limiter);
+#define QY(o) L1[MG_I3(d, i, jj + (o), k, t)]
+#define MY(o) f.maskS[MG_I3(d, i, jj + (o), k, t)]
+    return MG_ADV_FLUX_H(FAM, vTr(jj), cfl, a.advParm, QY, MY);
+#undef QY
+#undef MY
   };
   const long q = MG_I2(d, i, j, t);
   a.adv2[q3] = L1[q3] - dT * f.recip_hFacC[q3] * f.recip_drF[k - 1] * f.recip_rA[q] *
                                (afy(j + 1) - afy(j) - a.tr[q3] * (vTr(j + 1) - vTr(j))) * f.maskInC[q];
 }
-__global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) { adv_y_body(d, f, a, mg_xcd_block()); }
+template <int FAM>
+__global__ void __launch_bounds__(256) k_adv_y(Dims d, Fields f, TracerArgs a) { adv_y_body<FAM>(d, f, a, mg_xcd_block()); }
 
 // vertical pass + advective tendency (gad_advection.F k = Nr..1 loop) on the horizontally
 // advected tracer L (and, GAD_MULTIDIM_COMPRESSIBLE, the local volume V, :1036-1057):
 // gAdv = (loc - T)/dT, or (tmpTrac - T*vol)/(rA drF hFac dT) in the compressible form
-template <bool COMP>
+template <bool COMP, int FAM>
 __device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const Fields &f, const TracerArgs &a,
                                            const double *__restrict__ L2, const double *__restrict__ V, int lb) {
   MG_PLANE_LB(1, d.sNx, 1, d.sNy, z, lb)
@@ -209,19 +373,8 @@ __device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const
   auto rtr = [&](int kk) { return (kk <= 1 || kk > Nr) ? 0.0 : a.advW[MG_I3(d, i, j, kk, t)] * rA * MC(kk - 1); };
   auto fver = [&](int kk) {   // fVerT through the top of level kk, 0 at kk = 1 and below Nr
     if (kk <= 1 || kk > Nr) return 0.0;
-    const int km2 = kk - 2 > 1 ? kk - 2 : 1, km1 = kk - 1 > 1 ? kk - 1 : 1, kp1 = kk + 1 < Nr ? kk + 1 : Nr;
-    const double Rjp = (LT(kk) - LT(kp1)) * MC(kp1);
-    const double Rj = (LT(km1) - LT(kk)) * MC(kk) * MC(km1);
-    const double Rjm = (LT(km2) - LT(km1)) * MC(km1);
-    const double cfl = fabs(a.advW[MG_I3(d, i, j, kk, t)] * dT * f.recip_drC[kk - 1]);
-    const double oneSixth = 1.0 / 6.0;
-    const double d0 = (2.0 - cfl) * (1.0 - cfl) * oneSixth, d1 = (1.0 - cfl * cfl) * oneSixth;
-    const double rT = rtr(kk);
-    if (!a.limiter)   // GAD_DST3_ADV_R (gad_dst3_adv_r.F:70-119)
-      return 0.5 * (rT + fabs(rT)) * (LT(kk) + (d0 * Rj + d1 * Rjp)) + 0.5 * (rT - fabs(rT)) * (LT(km1) - (d0 * Rj + d1 * Rjm));
-    const double psiP = dst3fl_limit(d0, d1, dst3fl_theta(Rj, Rjm), cfl);
-    const double psiM = dst3fl_limit(d0, d1, dst3fl_theta(Rj, Rjp), cfl);
-    return 0.5 * (rT + fabs(rT)) * (LT(kk) + psiM * Rj) + 0.5 * (rT - fabs(rT)) * (LT(km1) - psiP * Rj);
+    MG_ADV_FLUX_R_RETURN(FAM, rtr(kk), fabs(a.advW[MG_I3(d, i, j, kk, t)] * dT * f.recip_drC[kk - 1]), kk, Nr, a.advParm,
+                         p.rkSign, LT, MC);
   };
   const double kp1Msk = (k == Nr) ? 0.0 : 1.0;
   const double rTrans = rtr(k), rTransKp = kp1Msk * rtr(k + 1);
@@ -238,10 +391,10 @@ __device__ __forceinline__ void adv_r_body(const Dims &d, const Params &p, const
 #undef MC
 #undef LT
 }
-template <bool COMP>
+template <bool COMP, int FAM>
 __global__ void __launch_bounds__(256) k_adv_r(Dims d, Params p, Fields f, TracerArgs a, const double *__restrict__ L2,
                                                const double *__restrict__ V) {
-  adv_r_body<COMP>(d, p, f, a, L2, V, mg_xcd_block());
+  adv_r_body<COMP, FAM>(d, p, f, a, L2, V, mg_xcd_block());
 }
 
 // ---------------------------------------------------------------------------
@@ -334,8 +487,9 @@ __device__ __forceinline__ void advg_fill_point(const Dims &d, int face, int edg
   L[MG_FR(d, di, dj)] = L[MG_FR(d, si, sj)];
 }
 
-// the X (ydir = 0) or Y (1) DST3FL face flux of a pass into G, on the tiles that compute
-// it (GAD_DST3FL_ADV_X over i = 3-OLx..sNx+OLx-1, _Y over j = 3-OLy..sNy+OLy-1)
+// the X (ydir = 0) or Y (1) face flux of a pass into G, on the tiles that compute it, over the
+// scheme's own faces (GAD_DST3FL_ADV_X: i = 3-OLx..sNx+OLx-1, _Y: j = 3-OLy..sNy+OLy-1)
+template <int FAM>
 __device__ __forceinline__ void advg_flux_point(const Dims &d, const Fields &f, const TracerArgs &a, int ipass, int ydir,
                                                 bool cube, int face, int edges, int i, int j, int k, int t,
                                                 const double *Lc, double *G) {
@@ -346,18 +500,22 @@ __device__ __forceinline__ void advg_flux_point(const Dims &d, const Fields &f, 
   const int q = MG_FR(d, i, j);
   const double dT = a.dT, drF = f.drF[k - 1];
   double af = 0.0;
-  if (!ydir && i >= 3 - d.OLx && i <= d.sNx + d.OLx - 1) {
+  if (!ydir && i >= AdvFaces<FAM>::lo - d.OLx && i <= d.sNx + d.OLx + AdvFaces<FAM>::hi) {
     const double uTr = a.advU[q3] * (f.dyG[MG_I2(d, i, j, t)] * drF * f.hFacW[q3]);
     const double cfl = fabs(a.advU[q3] * dT * f.recip_dxC[MG_I2(d, i, j, t)]);
-    af = dst3fl_h(uTr, cfl, Lc[MG_FR(d, i - 2, j)], Lc[MG_FR(d, i - 1, j)], Lc[q], Lc[MG_FR(d, i + 1, j)],
-                  mask_loc(d, f, cube, edges, true, i - 1, j, k, t), mask_loc(d, f, cube, edges, true, i, j, k, t),
-                  mask_loc(d, f, cube, edges, true, i + 1, j, k, t), a.limiter);
-  } else if (ydir && j >= 3 - d.OLy && j <= d.sNy + d.OLy - 1) {
+#define QX(o) Lc[MG_FR(d, i + (o), j)]
+#define MX(o) mask_loc(d, f, cube, edges, true, i + (o), j, k, t)
+    af = MG_ADV_FLUX_H(FAM, uTr, cfl, a.advParm, QX, MX);
+#undef QX
+#undef MX
+  } else if (ydir && j >= AdvFaces<FAM>::lo - d.OLy && j <= d.sNy + d.OLy + AdvFaces<FAM>::hi) {
     const double vTr = a.advV[q3] * (f.dxG[MG_I2(d, i, j, t)] * drF * f.hFacS[q3]);
     const double cfl = fabs(a.advV[q3] * dT * f.recip_dyC[MG_I2(d, i, j, t)]);
-    af = dst3fl_h(vTr, cfl, Lc[MG_FR(d, i, j - 2)], Lc[MG_FR(d, i, j - 1)], Lc[q], Lc[MG_FR(d, i, j + 1)],
-                  mask_loc(d, f, cube, edges, false, i, j - 1, k, t), mask_loc(d, f, cube, edges, false, i, j, k, t),
-                  mask_loc(d, f, cube, edges, false, i, j + 1, k, t), a.limiter);
+#define QY(o) Lc[MG_FR(d, i, j + (o))]
+#define MY(o) mask_loc(d, f, cube, edges, false, i, j + (o), k, t)
+    af = MG_ADV_FLUX_H(FAM, vTr, cfl, a.advParm, QY, MY);
+#undef QY
+#undef MY
   }
   G[q] = af;
 }
@@ -426,12 +584,13 @@ __global__ void __launch_bounds__(256) k_advg_fill(Dims d, Fields f, double *loc
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   advg_fill_point(d, f.tileFace[t], f.tileEdge[t], ipass, stage, c, MG_LEVEL(loc, d, k, t));
 }
+template <int FAM>
 __global__ void __launch_bounds__(256) k_advg_flux(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube) {
   MG_PLANE(1 - d.OLx, d.nx, 1 - d.OLy, d.ny, z)
   const int t = d.t0 + z / d.Nr, k = z % d.Nr + 1;
   if (i > d.sNx + d.OLx || j > d.sNy + d.OLy) return;
   const int face = cube ? f.tileFace[t] : 0, edges = cube ? f.tileEdge[t] : 0;
-  advg_flux_point(d, f, a, ipass, ydir, cube != 0, face, edges, i, j, k, t, MG_LEVEL(a.adv1, d, k, t),
+  advg_flux_point<FAM>(d, f, a, ipass, ydir, cube != 0, face, edges, i, j, k, t, MG_LEVEL(a.adv1, d, k, t),
                   MG_LEVEL(f.gTscr, d, k, t));
 }
 __global__ void __launch_bounds__(256) k_advg_upd(Dims d, Fields f, TracerArgs a, int ipass, int ydir, int cube, int comp) {
@@ -1388,21 +1547,21 @@ hipError_t launch_tracer_step(const Dims &d, const Params &p, const Fields &f, c
     const dim3 fgrd(mg_plane_blocks(d.nx, d.ny, d.nT * d.Nr));
     const bool cube = p.cubeCorners != 0, comp = p.multiDimCompressible != 0;
     if (!cube && !comp) {   // lat-lon, 2 passes: fused per-point X and Y passes
-      MG_LAUNCH(k_adv_x, fgrd, blk, 0, s, d, f, a);
-      MG_LAUNCH(k_adv_y, grd, blk, 0, s, d, f, a);
-      MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, a.adv2, a.adv2);
+      MG_ADV_FAMILY(a.advFamily, MG_LAUNCH(k_adv_x<FAM>, fgrd, blk, 0, s, d, f, a));
+      MG_ADV_FAMILY(a.advFamily, MG_LAUNCH(k_adv_y<FAM>, grd, blk, 0, s, d, f, a));
+      MG_ADV_FAMILY(a.advFamily, MG_LAUNCH((k_adv_r<false, FAM>), grd, blk, 0, s, d, p, f, a, a.adv2, a.adv2));
     } else {                // the general form: explicit passes over the whole slab
       MG_LAUNCH(k_advg_init, fgrd, blk, 0, s, d, f, a, (int)comp);
       const unsigned cgrd = (unsigned)((4L * d.OLx * d.OLy * d.nT * d.Nr + 255) / 256);
       for (int ipass = 1; ipass <= (cube ? 3 : 2); ipass++)
         for (int ydir = 0; ydir < 2; ydir++) {
           if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, a.adv1, ipass, 2 * ydir);
-          MG_LAUNCH(k_advg_flux, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube);
+          MG_ADV_FAMILY(a.advFamily, MG_LAUNCH(k_advg_flux<FAM>, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube));
           if (cube) MG_LAUNCH(k_advg_fill, dim3(cgrd), blk, 0, s, d, f, a.adv1, ipass, 2 * ydir + 1);
           MG_LAUNCH(k_advg_upd, fgrd, blk, 0, s, d, f, a, ipass, ydir, (int)cube, (int)comp);
         }
-      if (comp) MG_LAUNCH(k_adv_r<true>, grd, blk, 0, s, d, p, f, a, a.adv1, a.adv2);
-      else MG_LAUNCH(k_adv_r<false>, grd, blk, 0, s, d, p, f, a, a.adv1, a.adv1);
+      if (comp) MG_ADV_FAMILY(a.advFamily, MG_LAUNCH((k_adv_r<true, FAM>), grd, blk, 0, s, d, p, f, a, a.adv1, a.adv2));
+      else MG_ADV_FAMILY(a.advFamily, MG_LAUNCH((k_adv_r<false, FAM>), grd, blk, 0, s, d, p, f, a, a.adv1, a.adv1));
     }
   }
   // GM/Redi fluxes as a template switch: without them the kernel holds half the registers

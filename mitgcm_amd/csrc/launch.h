@@ -78,7 +78,7 @@ hipError_t launch_mon_stats(const Dims &, const MonSpecs &, int, double *, int, 
 
 // ---- kernels_ptracers.hip (through kernels_step.hip)
 bool ptr_batch_ok(const Dims &, const Params &, bool md);
-hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int, int, int,
-                                 int, const int *, hipStream_t, int *nLaunch = nullptr);
+hipError_t launch_ptracers_batch(const Dims &, const Params &, const Fields &, const TracerArgs *, const int *, int,
+                                 const int *nMdFam, int, int, const int *, hipStream_t, int *nLaunch = nullptr);
 
 }  // namespace mgcm

@@ -245,6 +245,7 @@ struct mgcm_model {
   TracerArgs *d_ptrTab = nullptr;  // [2 parities][n] the batched kernels' table
   int *d_ptrList = nullptr;        // [2][n]: the multi-dimensional tracers, then every tracer in launch order
   int ptrNMd = 0, ptrNGM = 0;       // multi-dimensional tracers; tracers that take GM/Redi (first in launch order)
+  int ptrNMdFam[MG_ADV_NFAM] = {0, 0, 0};   // the multi-dimensional tracers per scheme family (their list is sorted by it)
   bool ptrTabDirty = true;
   // THERMODYNAMICS of a sharded step on the second stream (mgcm_step_phase 16): 1 forked after
   // DO_OCEANIC_PHYS (joined before UPDATE_R_STAR), 2 to fork after CALC_DIV_GHAT, 3 forked
@@ -1545,11 +1546,23 @@ int mgcm_init(mgcm_model *m) {
   m->p.recip_rSphere = sph ? 1.0 / ext("rSphere", 6370.0e3) : 0.0;   // ini_parms.F:1334
   if (ext("integr_GeoPot", 2.0) != 2.0) return set_err("mgcm_init: only integr_GeoPot = 2 is implemented");
   // tracer advection schemes implemented on the device: 2 (C2), 3 (U3) and 4 (C4) inside
-  // GAD_CALC_RHS with Adams-Bashforth on the tendency, 30 (DST3) and 33 (DST3 flux-limited)
-  // multi-dimensional; the vertical scheme must match the horizontal one
+  // GAD_CALC_RHS with Adams-Bashforth on the tendency; multi-dimensional 30 (DST3), 33 (DST3
+  // flux-limited), 1 (upwind), 20 (DST2) and 7 (OS7MP); the vertical scheme must match the
+  // horizontal one.  (77 and the other flux limiters, SOM, PPM / PQM: not restated.)
+  auto mdScheme = [&](int s) { return s == 30 || s == 33 || s == 1 || s == 20 || s == 7; };
   auto okScheme = [&](int s, const char *vname) {
-    return (s == 2 || s == 3 || s == 4 || ((s == 30 || s == 33) && m->p.multiDimAdvection)) &&
-           ext(vname, (double)s) == (double)s;
+    return (s == 2 || s == 3 || s == 4 || (mdScheme(s) && m->p.multiDimAdvection)) && ext(vname, (double)s) == (double)s;
+  };
+  // OS7MP reaches 4 cells: GAD_CHECK wants an overlap of 4 (gad_init_fixed.F:52), 8 on the cube
+  // (gad_init_fixed.F:178-181 doubles it), where the wider reach across face edges is not restated
+  auto os7mpRefused = [&](int s, const char *who) {   // (0: accepted)
+    if (s != 7 || !m->p.multiDimAdvection) return 0;
+    if (m->uvMap)
+      return set_err("mgcm_init: %s 7 (OS7MP) on an EXCH2 topology is not implemented: the cube needs OLx, OLy >= 8 "
+                     "(gad_init_fixed.F:178-181) and the 4-cell reach across face edges is not restated", who);
+    if (m->d.OLx < 4 || m->d.OLy < 4)
+      return set_err("mgcm_init: %s 7 (OS7MP) needs OLx, OLy >= 4 (GAD_CHECK: Overlap Size too small)", who);
+    return 0;
   };
   auto wideScheme = [&](int s) { return s == 3 || s == 4; };
   if (((m->p.tempStepping && wideScheme(m->p.tempAdvScheme)) || (m->p.saltStepping && wideScheme(m->p.saltAdvScheme))) &&
@@ -1563,7 +1576,6 @@ int mgcm_init(mgcm_model *m) {
   // the cube's multi-dimensional split (3 face-dependent passes with corner fills,
   // gad_advection.F:339-367) runs the general pass kernels (kernels_thermo.hip k_advg_*),
   // which need the tile face / edge table of the EXCH2 topology and OLx = OLy (corner fills)
-  auto mdScheme = [&](int s) { return s == 30 || s == 33; };
   if (m->uvMap && ((m->p.tempStepping && mdScheme(m->p.tempAdvScheme)) || (m->p.saltStepping && mdScheme(m->p.saltAdvScheme)))) {
     if (!m->f.tileFace) return set_err("mgcm_init: multi-dimensional advection on EXCH2 needs the tile face table");
     if (m->d.OLx != m->d.OLy) return set_err("mgcm_init: cube multi-dimensional advection needs OLx = OLy");
@@ -1577,6 +1589,8 @@ int mgcm_init(mgcm_model *m) {
     return set_err("mgcm_init: tempAdvScheme %d not implemented on the device", m->p.tempAdvScheme);
   if (m->p.saltStepping && !okScheme(m->p.saltAdvScheme, "saltVertAdvScheme"))
     return set_err("mgcm_init: saltAdvScheme %d not implemented on the device", m->p.saltAdvScheme);
+  if (m->p.tempStepping && os7mpRefused(m->p.tempAdvScheme, "tempAdvScheme")) return -1;
+  if (m->p.saltStepping && os7mpRefused(m->p.saltAdvScheme, "saltAdvScheme")) return -1;
   if (m->p.useGMRedi && m->p.GM_AdvForm && m->p.GM_skewflx != 0.0)
     return set_err("mgcm_init: GM_AdvForm needs GM_skewflx = 0 (gmredi_readparms.F:243-244)");
   // pkg/ptracers: a tracer is accepted with exactly the options salt would be accepted with
@@ -1598,6 +1612,9 @@ int mgcm_init(mgcm_model *m) {
     }
     if (!okScheme(s, "PTRACERS_vertAdvScheme"))
       return set_err("mgcm_init: pTracer%02d: advScheme %d not implemented on the device", no, s);
+    char who[32];
+    snprintf(who, sizeof who, "pTracer%02d: advScheme", no);
+    if (os7mpRefused(s, who)) return -1;
   }
   if (m->p.eosType != 0 && m->p.eosType != 1) return set_err("mgcm_init: eosType %d not implemented", m->p.eosType);
   if (m->d.Nr > 64) return set_err("mgcm_init: Nr = %d > 64 (column kernels hold a column in one workgroup)", m->d.Nr);
@@ -1733,7 +1750,10 @@ static void tracer_args_common(const mgcm_model *m, int scheme, bool res, Tracer
   a.dT = m->p.deltaTtracer;
   a.multiDim = scheme_multi_dim(m->p, a.advection, scheme);
   a.useAB = scheme_is_ab(scheme);
-  a.limiter = scheme == 33;   // DST3 (30) without, DST3FL (33) with the flux limiter
+  // the flux function the passes are compiled for, and its parameter: DST3 (30) without, DST3FL
+  // (33) with the flux limiter; upwind (1) and DST2 (20) are GAD_DST2U1's xLimit = 0 / 1
+  a.advFamily = scheme == 7 ? MG_ADV_OS7MP : (scheme == 1 || scheme == 20) ? MG_ADV_DST2U1 : MG_ADV_DST3;
+  a.advParm = scheme == 33 || scheme == 20;
   a.scheme = scheme;
   a.advU = res ? m->f.uRes : m->f.uVel;
   a.advV = res ? m->f.vRes : m->f.vVel;
@@ -1838,10 +1858,13 @@ static int ptr_tables_sync(mgcm_model *m) {
       const int c = (a.gm ? 0 : 3) + (a.multiDim ? 2 : (a.scheme == 2 ? 1 : 0));
       if (c == cls) lists[n + na++] = i;
     }
-  for (int i = 0; i < n; i++) {
-    if (tab[i].multiDim) lists[m->ptrNMd++] = i;
-    if (tab[i].gm) m->ptrNGM++;
+  for (int fam = 0; fam < MG_ADV_NFAM; fam++) {   // one set of pass launches per family (launch_ptracers_batch)
+    m->ptrNMdFam[fam] = 0;
+    for (int i = 0; i < n; i++)
+      if (tab[i].multiDim && tab[i].advFamily == fam) { lists[m->ptrNMd++] = i; m->ptrNMdFam[fam]++; }
   }
+  for (int i = 0; i < n; i++)
+    if (tab[i].gm) m->ptrNGM++;
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipStreamSynchronize(m->stream));
   HIPCHK(hipMemcpy(m->d_ptrTab, tab.data(), tab.size() * sizeof(TracerArgs), hipMemcpyHostToDevice));
@@ -1861,7 +1884,7 @@ static int ptracers_on(mgcm_model *m, hipStream_t st) {
   if (m->ptrTabDirty) return set_err("ptracers_on: the passive tracers' device table is stale");
   if (ptr_batched(m)) {
     m->ptrRoute = 2;
-    TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMd, n,
+    TIMED(K_TEMP, launch_ptracers_batch(m->d, m->p, m->f, m->d_ptrTab + (size_t)m->ptrFlip * n, m->d_ptrList, n, m->ptrNMdFam, n,
                                         m->ptrNGM, m->d_ctr, st, &m->ptrLaunches));
   } else {
     m->ptrRoute = 1;

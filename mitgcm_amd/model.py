@@ -26,8 +26,10 @@ STATE_1D = ("tRef", "sRef", "pRef4EOS", "phiRefC")
 STATE_3D = ("uVel", "vVel", "wVel", "theta", "salt", "gU", "gV", "guNm1", "gvNm1", "gtNm1", "gsNm1", "rhoInSitu",
             "IVDConvCount", "sigmaR", "Kwx", "Kwy", "Kwz", "Kux", "Kvy", "uVelD", "vVelD", "uNM1", "vNM1",
             "totPhiHyd", "alphaRho", "del2u", "del2v", "Kuz", "Kvz", "GM_PsiX", "GM_PsiY")
-# 3-D work fields of DYNAMICS a get() may read (CALC_PHI_HYD's phi and MOM_CALC_RTRANS's dWtrans)
-WORK_3D = ("phiHydC", "dWtC", "dWtU", "dWtV")
+# 3-D work fields a get() may read: DYNAMICS' (CALC_PHI_HYD's phi and MOM_CALC_RTRANS's dWtrans) and
+# THERMODYNAMICS' (GAD_ADVECTION's tendency of the last multi-dimensional tracer stepped -- salt,
+# else theta; a passive tracer has its own -- and GM_AdvForm's residual flow)
+WORK_3D = ("phiHydC", "dWtC", "dWtU", "dWtV", "gAdv", "uRes", "vRes", "wRes")
 STATE_2D = ("etaN", "etaH", "fu", "fv", "SST", "lambdaThetaClimRelax", "surfaceForcingT", "surfaceForcingS",
             "Qnet", "EmPmR", "SSS", "lambdaSaltClimRelax", "etaNm1", "rStarFacC", "rStarFacW", "rStarFacS",
             "rStarExpC", "rStarExpW", "rStarExpS", "rStarDhCDt", "rStarDhWDt", "rStarDhSDt", "PmEpR", "dEtaHdt")
@@ -50,6 +52,9 @@ def _dp(a):
 PTRACER_PARAMS = ("advScheme", "diffKh", "diffKr", "useGMRedi", "surfRelaxTau", "surfRelaxVal", "interiorSource",
                   "EvPrRn")
 PTRACERS_MAX = 99   # PTRACERS_SIZE.h: two digits in every name
+# the direct-space-time schemes the device carries (multi-dimensional, no Adams-Bashforth):
+# DST3, DST3FL, first-order upwind, DST2, OS7MP
+MULTIDIM_SCHEMES = (30, 33, 1, 20, 7)
 
 
 def ptracer_name(i):
@@ -138,9 +143,10 @@ class Model:
         g = self.g
         # A model-wide side effect (README, "Passive tracers"): multiDimAdvection is .TRUE. by
         # default in the reference (set_defaults.F); a configuration whose theta and salt never
-        # needed it leaves it unset, which the device takes as off, and a DST tracer needs it.
+        # needed it leaves it unset, which the device takes as off, and a DST tracer (30, 33, 1,
+        # 20, 7) needs it.
         # An explicit 0 is left alone: mgcm_init then refuses the tracer's scheme.
-        if "multiDimAdvection" not in self.params and any(int(sp.get("advScheme", 2)) in (30, 33) for sp in specs):
+        if "multiDimAdvection" not in self.params and any(int(sp.get("advScheme", 2)) in MULTIDIM_SCHEMES for sp in specs):
             self.params["multiDimAdvection"] = 1
             check(L.mgcm_set_param(self.h, b"multiDimAdvection", 1.0), "mgcm_set_param(multiDimAdvection)")
         for no, sp in enumerate(specs, 1):
@@ -200,6 +206,11 @@ class Model:
         self.put(name, arr)
 
     def get(self, name):
+        """A field by name, halos included.  Besides the grid and the state: the work fields of
+        WORK_3D.  'gAdv' is one scratch field for theta and salt, GAD_ADVECTION's tendency of the
+        last multi-dimensional tracer the last THERMODYNAMICS stepped (salt's when both are; a
+        passive tracer has its own, not readable here); 'uRes', 'vRes', 'wRes' hold GM_AdvForm's
+        residual flow only where gm_res_flow() is true."""
         a = np.zeros(self._shape(name))
         check(lib().mgcm_get(self.h, name.encode(), _dp(a), a.size), "mgcm_get(%s)" % name)
         return a
@@ -313,7 +324,7 @@ class Model:
         """True when the last THERMODYNAMICS issued formed GM_AdvForm's residual flow as fields
         (mgcm_get_param 'gmResFlow': k_gm_residual_flow ran, and the multi-dimensional advection of
         theta, salt and the passive tracers took uRes, vRes, wRes): useGMRedi with GM_AdvForm and
-        at least one stepped tracer on scheme 30 or 33.  A replayed step graph keeps what it was
+        at least one stepped tracer on a multi-dimensional scheme (30, 33, 1, 20, 7).  A replayed step graph keeps what it was
         captured with."""
         return lib().mgcm_get_param(self.h, b"gmResFlow") != 0.0
 
